@@ -7,8 +7,22 @@ pool/GEMM kernels, fused softmax-CE, SGD-momentum multi-precision update, and
 — for N>1 ranks — bucketed RCCL all-reduce overlapped with backward
 (kvstore 'dist_sync' semantics).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (N>1 is launched by the driver via torch.distributed.run, one rank per GPU.)
+
+A plain run sets up, warms up, times K steps and prints one JSON line.
+--full adds the auxiliary measurements that need runs of their own (the
+bs128 matched-batch row).
+
+--dump-outputs DIR writes what one step of the timed path computes (loss,
+logits, a seeded sample of the updated weights, BN running stats) as
+DIR/<name>.npy, so that two builds can be compared array for array. Inputs
+and init are seeded. The dumped step is run once more after the timed ones,
+untimed, from the state the model had before warmup: the wgrad split-K
+kernels sum fp32 partials with atomics in no fixed order, and K chained SGD
+steps amplify that last-bit noise (measured on an MI355X at bs4096: one bf16
+ulp after 2 steps, 1.7 in the logits after 4, 8.75 after 13), so only a step
+whose weights are the same in every run gives the same arrays in every run.
 
 Reference numbers this is measured against: BASELINE.md (ResNet-50 training
 images/sec, 1xV100 fp32: 298.51 @bs32, 363.69 @bs128).
@@ -21,7 +35,78 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+# --dump-outputs budget: 64 MB in all; the logits get at most half of it and
+# every parameter tensor contributes at most this many sampled elements
+DUMP_LOGITS_MAX_BYTES = 32 << 20
+DUMP_PARAM_SAMPLE = 16384
+DUMP_TOTAL_MAX_BYTES = 64 << 20
+
+
+def _train_state(mod):
+    """Every tensor a training step reads and writes in place: weights,
+    optimizer state, BN buffers."""
+    from dtmx.module.module import _flatten_state
+
+    if mod._use_fused_sgd and mod._bucketer is not None:
+        tensors = list(mod._bucketer.state_tensors())
+    else:
+        tensors = [p.data for p in mod.symbol.parameters()]
+        for i in sorted(mod._updater.states.keys()):
+            tensors += _flatten_state(mod._updater.states[i])
+    return tensors + [b.data for b in mod.symbol.buffers()]
+
+
+def snapshot_state(mod):
+    opt = mod._optimizer
+    return ([t.clone() for t in _train_state(mod)], opt.num_update,
+            dict(getattr(opt, "_index_update_count", {})))
+
+
+def restore_state(mod, snap):
+    saved, num_update, counts = snap
+    with torch.no_grad():
+        for t, s in zip(_train_state(mod), saved):
+            t.copy_(s)
+    mod._optimizer.num_update = num_update
+    if hasattr(mod._optimizer, "_index_update_count"):
+        mod._optimizer._index_update_count = dict(counts)
+
+
+def dump_outputs(mod, out_dir):
+    """Write the last step's results as float32/float64 .npy files. Samples
+    use a fixed CPU generator seed, so the same elements are picked every
+    run."""
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(0)
+    arrays = {}
+    if mod._loss is not None:
+        arrays["loss"] = mod._loss.detach().double().reshape(1).cpu().numpy()
+    logits = mod.get_outputs()[0].detach()
+    rows = max(1, DUMP_LOGITS_MAX_BYTES // (4 * max(1, logits[0].numel())))
+    if logits.shape[0] > rows:
+        idx = torch.randperm(logits.shape[0], generator=g)[:rows].sort().values
+        logits = logits[idx.to(logits.device)]
+    arrays["logits"] = logits.float().cpu().numpy()
+    args_, auxs = mod._classified_named_tensors()
+    sampled = []
+    for _, p in args_.items():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            idx = torch.randint(flat.numel(), (DUMP_PARAM_SAMPLE,), generator=g)
+            flat = flat[idx.to(flat.device)]
+        sampled.append(flat.float().cpu())
+    arrays["params_sample"] = torch.cat(sampled).numpy()
+    if auxs:
+        arrays["aux_stats"] = torch.cat(
+            [b.detach().reshape(-1).float().cpu() for b in auxs.values()]).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_TOTAL_MAX_BYTES, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -36,7 +121,14 @@ def main():
     ap.add_argument("--num-layers", type=int, default=50)
     ap.add_argument("--image-shape", type=str, default="3,224,224")
     ap.add_argument("--dtype", type=str, default="bfloat16")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the last timed step's results to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the auxiliary measurements (bs128 "
+                         "matched-batch row); off by default")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import dtmx
     from dtmx.io import SyntheticDataIter
@@ -48,6 +140,7 @@ def main():
     dist_mode = world > 1
 
     torch.manual_seed(1234)
+    np.random.seed(1234)  # SyntheticDataIter draws its batch from numpy
     if torch.cuda.is_available():
         # clamp in case the launcher passes more ranks than devices (RCCL
         # itself refuses duplicate devices in one communicator, so world>1
@@ -98,6 +191,8 @@ def main():
             mod.forward_backward(batch)
             mod.update()
 
+    snap = snapshot_state(mod) if args.dump_outputs else None
+
     for _ in range(args.warmup):
         step()
 
@@ -129,6 +224,15 @@ def main():
               f"{torch.cuda.max_memory_reserved() / 2**30:.1f} GiB",
               file=sys.stderr)
 
+    if args.dump_outputs:
+        # untimed: one more step of the timed path from the pre-warmup state
+        # (every rank takes part in its collectives; rank 0 writes)
+        restore_state(mod, snap)
+        step()
+        barrier_sync()
+        if rank == 0:
+            dump_outputs(mod, args.dump_outputs)
+
     n_gpus = world if dist_mode else 1
     imgs = B * n_gpus * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
@@ -139,11 +243,12 @@ def main():
     model_name = (f"{args.network}-{args.num_layers}" if uses_layers
                   else args.network)
 
-    # matched-batch auxiliary row (outside the timed region): the headline
-    # uses the large-batch config; the published V100 baseline is bs128, so
-    # report a bs128 measurement too for an apples-per-apples multiplier.
+    # matched-batch auxiliary row (--full only, outside the timed region): the
+    # headline uses the large-batch config; the published V100 baseline is
+    # bs128, so report a bs128 measurement too for an apples-per-apples
+    # multiplier.
     aux = None
-    if (rank == 0 and not dist_mode and device.type == "cuda"
+    if (args.full and rank == 0 and not dist_mode and device.type == "cuda"
             and args.network == "resnet" and B != 128
             and os.environ.get("DTMX_BENCH_AUX", "1") == "1"):
         try:

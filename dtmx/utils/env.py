@@ -23,7 +23,8 @@ Engine / debugging:
   DTMX_CHECK            1 = extra numerics checks in the op wrappers
   DTMX_PRINT_MEM        1 = print peak HBM use after bench
   DTMX_SEED / DTMX_TEST_SEED   RNG seeds (dtmx.random / tests)
-  DTMX_BENCH_AUX        0 = skip bench.py's bs128 matched-batch aux row
+  DTMX_BENCH_AUX        0 = skip the bs128 matched-batch aux row of
+                        `bench.py --full`
 
 Kernel dispatch (all measured defaults; the off-switches exist for A/B —
 see profiles/resnet50_mi355x.md for the numbers behind each):

@@ -530,6 +530,48 @@ def test_bench_json_contract(tmp_path):
     assert d["config"]["parallelism"] == "dp1"
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes one step of the timed path, taken from the
+    seeded pre-warmup state, as float .npy files (<= 64 MB in all): the dump
+    is the same from run to run, whatever --steps/--warmup/--full ran before
+    it (CPU run, so bit for bit)."""
+    import json as _json
+    import subprocess
+    import sys as _sys
+
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    env.pop("RANK", None)
+    env.pop("WORLD_SIZE", None)
+
+    def run(name, steps, warmup, *extra):
+        out = tmp_path / name
+        r = subprocess.run(
+            [_sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+             "--steps", str(steps), "--warmup", str(warmup),
+             "--batch-size", "4", "--num-layers", "18",
+             "--image-shape", "3,32,32", "--dump-outputs", str(out), *extra],
+            capture_output=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = _json.loads(lines[0])
+        arrays = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+        return d, arrays
+
+    d1, a1 = run("a", 1, 0)
+    d2, a2 = run("b", 3, 2, "--full")
+    assert (d1["steps"], d1["warmup"]) == (1, 0)
+    assert (d2["steps"], d2["warmup"]) == (3, 2)
+    assert d1["ms_per_step"] > 0 and d2["ms_per_step"] > 0
+    assert set(a1) == set(a2) == {"loss", "logits", "params_sample", "aux_stats"}
+    assert a1["logits"].shape == (4, 1000)
+    assert sum(a.nbytes for a in a1.values()) <= 64 << 20
+    for k, a in a1.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        assert np.isfinite(a).all(), k
+        np.testing.assert_array_equal(a, a2[k], err_msg=k)
+
+
 def test_bench_dist_contract_world2(tmp_path):
     """bench.py under the driver's multi-rank launch pattern (torchrun env:
     RANK/WORLD_SIZE/LOCAL_RANK/MASTER_*), world 2 on gloo/CPU: both ranks

@@ -19,6 +19,13 @@ from dtmx.models import get_symbol
 pytestmark = pytest.mark.gpu
 
 
+@pytest.fixture(autouse=True)
+def _seed_init():
+    """Weight init draws from torch's global generators; seed them so the
+    result does not depend on which tests ran earlier in the session."""
+    torch.manual_seed(0)
+
+
 def _teacher_data(n=2048, dim=64, classes=10, seed=0):
     """Linearly separable-ish task: labels from a fixed random teacher."""
     rng = np.random.RandomState(seed)

@@ -52,6 +52,11 @@ def _run_launcher_join(tmp_path):
         EPOCH_SLEEP="0.5",
         NUM_EPOCH="16",
         PYTHONPATH=ROOT,
+        # gloo/CPU scenario: the launcher pins worker i of a host to GPU i
+        # (LOCAL_RANK), and three workers share 127.0.0.1 here — hide the
+        # GPUs so the run does not need three of them
+        CUDA_VISIBLE_DEVICES="",
+        HIP_VISIBLE_DEVICES="",
     )
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
