@@ -16,6 +16,10 @@ std::vector<at::Tensor> conv_dgrad_bnfuse(const at::Tensor&, const at::Tensor&,
                                           const at::Tensor&, const at::Tensor&,
                                           const at::Tensor&, const at::Tensor&);
 std::vector<std::tuple<long, long, double>> wgrad_ws_stats();
+// dwconv.hip
+at::Tensor dwconv_fwd(const at::Tensor&, const at::Tensor&, long, long);
+at::Tensor dwconv_dgrad(const at::Tensor&, const at::Tensor&, long, long, long, long);
+at::Tensor dwconv_wgrad(const at::Tensor&, const at::Tensor&, long, long);
 // batchnorm.hip
 std::vector<at::Tensor> bn_fwd_train(const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, at::Tensor, at::Tensor,
@@ -99,6 +103,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stride"), py::arg("pad"), py::arg("H"), py::arg("W"),
         py::arg("acc") = c10::nullopt);
   m.def("conv_wgrad", &dtmx::conv_wgrad);
+  m.def("dwconv_fwd", &dtmx::dwconv_fwd, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("pad"));
+  m.def("dwconv_dgrad", &dtmx::dwconv_dgrad, py::arg("dy"), py::arg("w"),
+        py::arg("stride"), py::arg("pad"), py::arg("H"), py::arg("W"));
+  m.def("dwconv_wgrad", &dtmx::dwconv_wgrad, py::arg("x"), py::arg("dy"),
+        py::arg("stride"), py::arg("pad"));
   m.def("conv_dgrad_bnfuse", &dtmx::conv_dgrad_bnfuse, py::arg("dy"),
         py::arg("w"), py::arg("stride"), py::arg("pad"), py::arg("H"),
         py::arg("W"), py::arg("acc"), py::arg("y"), py::arg("xin"),

@@ -1,7 +1,8 @@
 """MobileNet v1 and v2 (reference example/image-classification/symbols/
-mobilenet.py, mobilenetv2.py). Depthwise convs route through
-GroupedConv2dNHWC (torch/MIOpen substrate — the hand HIP convs are dense
-gather kernels); pointwise 1x1s stay on the native path."""
+mobilenet.py, mobilenetv2.py). Depthwise 3x3s go through
+GroupedConv2dNHWC -> DF.depthwise_conv2d, the hand HIP depthwise kernels
+(dwconv.hip: fwd/dgrad/wgrad); pointwise 1x1s are the native implicit-GEMM
+path — no conv in either model uses the library substrate."""
 from __future__ import annotations
 
 import torch.nn as nn

@@ -7,6 +7,7 @@ Compute dtype bf16 (fp32 accumulate inside kernels); CPU path is fp32 torch.
 
 Reference kernel parity:
   conv fwd/dgrad/wgrad   <- src/operator/nn/convolution.cu (cuDNN/im2col)
+  depthwise 3x3 conv     <- src/operator/nn/depthwise_convolution_tf.cuh
   batch_norm fwd/bwd     <- src/operator/nn/batch_norm.cu:208-360
   pooling                <- src/operator/nn/pool.cuh
   relu / add(+relu)      <- mshadow_op elementwise kernels
@@ -99,6 +100,60 @@ def conv2d(x, w, stride: int = 1, padding: int = 0, want_stats: bool = False):
             return y, ps, pss
         return y
     return F.conv2d(x, w, None, stride, padding)
+
+
+# ----------------------------------------------------------- depthwise conv
+
+class _DepthwiseConvNHWC(torch.autograd.Function):
+    """Depthwise 3x3 (groups == C, multiplier 1) on the dwconv.hip kernels.
+    `w` is the parameter as stored, logical (C,1,3,3) = memory [C][3][3]."""
+
+    @staticmethod
+    def forward(ctx, x, w, stride, padding):
+        ext = require_ext()
+        ctx.save_for_backward(x, w)
+        ctx.stride = stride
+        ctx.padding = padding
+        return ext.dwconv_fwd(x, w, stride, padding)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = require_ext()
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.dwconv_dgrad(dy, w, ctx.stride, ctx.padding,
+                                  x.shape[2], x.shape[3])
+        if ctx.needs_input_grad[1]:
+            dw = ext.dwconv_wgrad(x, dy, ctx.stride, ctx.padding)
+        return dx, dw, None, None
+
+
+def _dwconv_in_envelope(x, w, stride, padding) -> bool:
+    """The cases dwconv.hip implements: 3x3, stride 1|2, pad 0|1 (same for H
+    and W), multiplier 1, C % 8 == 0, output non-empty."""
+    if x.dim() != 4 or w.dim() != 4 or not isinstance(stride, int) \
+            or not isinstance(padding, int):
+        return False
+    C = x.shape[1]
+    return (tuple(w.shape) == (C, 1, 3, 3) and C % 8 == 0 and x.numel() > 0
+            and stride in (1, 2) and padding in (0, 1)
+            and x.shape[2] + 2 * padding >= 3 and x.shape[3] + 2 * padding >= 3
+            and w.dtype == x.dtype and w.is_contiguous()
+            and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
+
+
+def depthwise_conv2d(x, w, stride: int = 1, padding: int = 0):
+    """Depthwise conv: x (N,C,H,W), w (C,1,k,k), groups == C.
+
+    GPU bf16/fp16 3x3 cases inside the kernel envelope run the hand HIP
+    depthwise kernels; everything else (CPU, fp32, C % 8 != 0, other kernel
+    sizes, DTMX_FALLBACK=dwconv) is torch's grouped conv."""
+    if _use_hip(x, w, op="dwconv") and _dwconv_in_envelope(x, w, stride, padding):
+        x = x.contiguous(memory_format=torch.channels_last)
+        return _DepthwiseConvNHWC.apply(x, w, stride, padding)
+    return F.conv2d(x, w, None, stride, padding, 1, x.shape[1])
 
 
 # --------------------------------------------------------------- batch norm

@@ -95,15 +95,20 @@ class BatchNorm2dNHWC(nn.Module):
 
 
 class GroupedConv2dNHWC(nn.Module):
-    """Grouped / depthwise conv (mobilenet, resnext). The hand HIP conv
-    kernels are dense-gather only, so groups>1 routes through torch's conv
-    on channels_last memory (MIOpen on ROCm) — the documented long-tail
-    substrate path; groups==1 uses Conv2dNHWC instead."""
+    """Grouped / depthwise conv (mobilenet, resnext); groups==1 uses
+    Conv2dNHWC instead. Depthwise (groups == in == out channels, mobilenet)
+    goes through DF.depthwise_conv2d — the hand HIP depthwise 3x3 kernels
+    (dwconv.hip) on GPU bf16/fp16. Every other groups>1 case (resnext's
+    cardinality-32 3x3s) has no hand kernel yet — the implicit-GEMM convs
+    are dense-gather only — and routes through torch's conv on
+    channels_last memory (MIOpen on ROCm), the documented long-tail
+    substrate path."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1,
                  padding=0, groups=1, bias=False):
         super().__init__()
         assert in_channels % groups == 0 and out_channels % groups == 0
+        self.depthwise = groups == in_channels == out_channels and groups > 1
         self.stride = stride
         self.padding = padding
         self.groups = groups
@@ -115,6 +120,12 @@ class GroupedConv2dNHWC(nn.Module):
 
     def forward(self, x):
         import torch.nn.functional as F
+        if self.depthwise:
+            y = DF.depthwise_conv2d(x, self.weight.to(x.dtype), self.stride,
+                                    self.padding)
+            if self.bias is not None:
+                y = y + self.bias.reshape(1, -1, 1, 1).to(y.dtype)
+            return y
         return F.conv2d(x, self.weight.to(x.dtype),
                         self.bias.to(x.dtype) if self.bias is not None else None,
                         self.stride, self.padding, 1, self.groups)
