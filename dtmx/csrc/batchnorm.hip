@@ -211,13 +211,16 @@ __global__ void bn_bwd_reduce_finalize_kernel(
 // block covers ncv channel-vectors (<=8) x (256/ncv) slab lanes; lane-strided
 // accumulate then LDS tree. Replaces both the per-channel serial loop
 // (measured 190us/call at nslabs=2048) and cross-block atomics.
+// ncv MUST be a power of two (host passes min(bn_cpb(cvecs), 8), as for the
+// fused reducers): the tree's halving offsets keep a channel column together
+// only while off % ncv == 0, and 256/ncv must not truncate or the last
+// partial lane re-reads slabs that lane 0 already summed.
 __global__ void slab_reduce2_kernel(const float* __restrict__ a,
                                     const float* __restrict__ b,
                                     float* __restrict__ outa,
                                     float* __restrict__ outb, uint32_t C,
-                                    uint32_t nslabs) {
+                                    uint32_t nslabs, uint32_t ncv) {
   const uint32_t cvecs = C / 8;
-  const uint32_t ncv = min(cvecs, 8u);
   const uint32_t lanes = blockDim.x / ncv;
   const uint32_t t = threadIdx.x;
   const uint32_t cv = blockIdx.x * ncv + t % ncv;
@@ -676,6 +679,27 @@ __global__ void bn_bwd_dx_col_kernel(const elem_t* __restrict__ x,
   }
 }
 
+// argument checks shared by the entry points; all run before any launch
+static void bn_check_x(const at::Tensor& x) {
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "bn: x must be NHWC");
+  TORCH_CHECK(x.size(1) % 8 == 0, "bn: C must be a multiple of 8, got ",
+              x.size(1));
+}
+
+static void bn_check_like(const at::Tensor& x, const at::Tensor& t,
+                          const char* name) {
+  TORCH_CHECK(t.sizes() == x.sizes() && t.scalar_type() == x.scalar_type() &&
+                  t.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "bn: ", name, " must be NHWC with the shape and dtype of x");
+}
+
+static void bn_check_vec(const at::Tensor& x, const at::Tensor& v,
+                         const char* name) {
+  TORCH_CHECK(v.numel() == x.size(1) && v.is_contiguous(), "bn: ", name,
+              " must be a contiguous vector of C elements");
+}
+
 static bool bn_col_on() {
   static const bool on = [] {
     const char* e = getenv("DTMX_BN_COL");
@@ -859,8 +883,12 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x, const at::Tensor& dy,
                                const at::Tensor& gamma, const at::Tensor& save_mean,
                                const at::Tensor& save_invstd, bool fuse_relu,
                                const at::Tensor& y, bool want_dres) {
+  bn_check_x(x);
+  bn_check_like(x, dy, "dy");
+  if (fuse_relu) bn_check_like(x, y, "y");  // y is only read as the relu mask
+  bn_check_vec(x, save_mean, "save_mean");
+  bn_check_vec(x, save_invstd, "save_invstd");
   uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  TORCH_CHECK(C % 8 == 0, "bn: C must be a multiple of 8, got ", C);
   uint32_t rows = N * H * W, cvecs = C / 8;
   uint32_t cpb = bn_cpb(cvecs);
   auto opt_f = x.options().dtype(at::kFloat);
@@ -1008,10 +1036,10 @@ std::vector<at::Tensor> bn_local_sums(const at::Tensor& x) {
                                          psumsq.data_ptr<float>(), rows, cvecs,
                                          cpb, rpb);
   });
-  uint32_t ncv = std::min(cvecs, 8u);
+  uint32_t ncv = std::min(cpb, 8u);  // power of two (slab_reduce2_kernel)
   slab_reduce2_kernel<<<(cvecs + ncv - 1) / ncv, 256, 0, s>>>(
       psum.data_ptr<float>(), psumsq.data_ptr<float>(), sum.data_ptr<float>(),
-      sumsq.data_ptr<float>(), C, nslabs);
+      sumsq.data_ptr<float>(), C, nslabs, ncv);
   return {sum, sumsq};
 }
 
@@ -1020,7 +1048,11 @@ std::vector<at::Tensor> bn_fwd_presummed(
     at::Tensor running_mean, at::Tensor running_var, double momentum, double eps,
     bool fuse_relu, const c10::optional<at::Tensor>& residual,
     const at::Tensor& sum, const at::Tensor& sumsq, long count) {
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), "bn: x must be NHWC");
+  bn_check_x(x);
+  if (residual.has_value()) bn_check_like(x, *residual, "residual");
+  bn_check_vec(x, sum, "sum");
+  bn_check_vec(x, sumsq, "sumsq");
+  TORCH_CHECK(count > 0, "bn: count must be positive, got ", count);
   uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   uint32_t rows = N * H * W, cvecs = C / 8;
   auto opt_f = x.options().dtype(at::kFloat);
@@ -1050,6 +1082,11 @@ std::vector<at::Tensor> bn_bwd_sums(const at::Tensor& x, const at::Tensor& dy,
                                     const at::Tensor& y,
                                     const at::Tensor& save_mean,
                                     const at::Tensor& save_invstd, bool fuse_relu) {
+  bn_check_x(x);
+  bn_check_like(x, dy, "dy");
+  if (fuse_relu) bn_check_like(x, y, "y");  // y is only read as the relu mask
+  bn_check_vec(x, save_mean, "save_mean");
+  bn_check_vec(x, save_invstd, "save_invstd");
   uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   uint32_t rows = N * H * W, cvecs = C / 8;
   uint32_t cpb = bn_cpb(cvecs);
@@ -1069,10 +1106,10 @@ std::vector<at::Tensor> bn_bwd_sums(const at::Tensor& x, const at::Tensor& dy,
         save_invstd.data_ptr<float>(), pdb.data_ptr<float>(),
         pdg.data_ptr<float>(), rows, cvecs, cpb, rpb, fuse_relu ? 1 : 0);
   });
-  uint32_t ncv = std::min(cvecs, 8u);
+  uint32_t ncv = std::min(cpb, 8u);  // power of two (slab_reduce2_kernel)
   slab_reduce2_kernel<<<(cvecs + ncv - 1) / ncv, 256, 0, s>>>(
       pdb.data_ptr<float>(), pdg.data_ptr<float>(), tdb.data_ptr<float>(),
-      tdg.data_ptr<float>(), C, nslabs);
+      tdg.data_ptr<float>(), C, nslabs, ncv);
   return {tdb, tdg};
 }
 
@@ -1081,6 +1118,14 @@ std::vector<at::Tensor> bn_bwd_dx_presummed(
     const at::Tensor& save_mean, const at::Tensor& save_invstd,
     const at::Tensor& gamma, const at::Tensor& tdb, const at::Tensor& tdg,
     long count, bool fuse_relu, bool want_dres) {
+  bn_check_x(x);
+  bn_check_like(x, dy, "dy");
+  if (fuse_relu) bn_check_like(x, y, "y");  // y is only read as the relu mask
+  bn_check_vec(x, save_mean, "save_mean");
+  bn_check_vec(x, save_invstd, "save_invstd");
+  bn_check_vec(x, tdb, "tdb");
+  bn_check_vec(x, tdg, "tdg");
+  TORCH_CHECK(count > 0, "bn: count must be positive, got ", count);
   uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   uint32_t cvecs = C / 8;
   auto dx = at::empty_like(x);
