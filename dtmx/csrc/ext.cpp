@@ -20,6 +20,11 @@ std::vector<std::tuple<long, long, double>> wgrad_ws_stats();
 at::Tensor dwconv_fwd(const at::Tensor&, const at::Tensor&, long, long);
 at::Tensor dwconv_dgrad(const at::Tensor&, const at::Tensor&, long, long, long, long);
 at::Tensor dwconv_wgrad(const at::Tensor&, const at::Tensor&, long, long);
+// gconv.hip
+at::Tensor gconv_fwd(const at::Tensor&, const at::Tensor&, long, long, long);
+at::Tensor gconv_dgrad(const at::Tensor&, const at::Tensor&, long, long, long, long,
+                       long);
+at::Tensor gconv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, bool);
 // batchnorm.hip
 std::vector<at::Tensor> bn_fwd_train(const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, at::Tensor, at::Tensor,
@@ -109,6 +114,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stride"), py::arg("pad"), py::arg("H"), py::arg("W"));
   m.def("dwconv_wgrad", &dtmx::dwconv_wgrad, py::arg("x"), py::arg("dy"),
         py::arg("stride"), py::arg("pad"));
+  m.def("gconv_fwd", &dtmx::gconv_fwd, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("pad"), py::arg("groups"));
+  m.def("gconv_dgrad", &dtmx::gconv_dgrad, py::arg("dy"), py::arg("w"),
+        py::arg("stride"), py::arg("pad"), py::arg("groups"), py::arg("H"),
+        py::arg("W"));
+  m.def("gconv_wgrad", &dtmx::gconv_wgrad, py::arg("x"), py::arg("dy"),
+        py::arg("stride"), py::arg("pad"), py::arg("groups"),
+        py::arg("w_channels_last") = false);
   m.def("conv_dgrad_bnfuse", &dtmx::conv_dgrad_bnfuse, py::arg("dy"),
         py::arg("w"), py::arg("stride"), py::arg("pad"), py::arg("H"),
         py::arg("W"), py::arg("acc"), py::arg("y"), py::arg("xin"),

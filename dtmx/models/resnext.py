@@ -1,7 +1,9 @@
 """ResNeXt (reference example/image-classification/symbols/resnext.py):
 bottleneck blocks whose 3x3 is a grouped conv (cardinality 32, width 4).
-Grouped 3x3s route through GroupedConv2dNHWC (torch/MIOpen substrate); the
-1x1s and BNs stay on the native HIP path with fused relu/residual."""
+Grouped 3x3s route through GroupedConv2dNHWC to the hand HIP grouped
+kernels (gconv.hip: 4, 8, 16, 32 channels per group in stages 1-4); the
+1x1s and BNs are on the native HIP path with fused relu/residual. bn2
+keeps its standalone statistics pass (no fused epilogue in gconv.hip)."""
 from __future__ import annotations
 
 import torch.nn as nn

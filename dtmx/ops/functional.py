@@ -8,6 +8,7 @@ Compute dtype bf16 (fp32 accumulate inside kernels); CPU path is fp32 torch.
 Reference kernel parity:
   conv fwd/dgrad/wgrad   <- src/operator/nn/convolution.cu (cuDNN/im2col)
   depthwise 3x3 conv     <- src/operator/nn/depthwise_convolution_tf.cuh
+  grouped 3x3 conv       <- src/operator/nn/convolution.cu (num_group > 1)
   batch_norm fwd/bwd     <- src/operator/nn/batch_norm.cu:208-360
   pooling                <- src/operator/nn/pool.cuh
   relu / add(+relu)      <- mshadow_op elementwise kernels
@@ -154,6 +155,72 @@ def depthwise_conv2d(x, w, stride: int = 1, padding: int = 0):
         x = x.contiguous(memory_format=torch.channels_last)
         return _DepthwiseConvNHWC.apply(x, w, stride, padding)
     return F.conv2d(x, w, None, stride, padding, 1, x.shape[1])
+
+
+# ------------------------------------------------------------- grouped conv
+
+class _GroupedConvNHWC(torch.autograd.Function):
+    """Grouped 3x3 (C_in == C_out, 4..32 channels per group) on the gconv.hip
+    MFMA kernels. `w` is the parameter as stored, logical (C,Cg,3,3), memory
+    contiguous or channels_last; dw comes back in the same layout."""
+
+    @staticmethod
+    def forward(ctx, x, w, stride, padding, groups):
+        ext = require_ext()
+        ctx.save_for_backward(x, w)
+        ctx.stride = stride
+        ctx.padding = padding
+        ctx.groups = groups
+        return ext.gconv_fwd(x, w, stride, padding, groups)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = require_ext()
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.gconv_dgrad(dy, w, ctx.stride, ctx.padding, ctx.groups,
+                                 x.shape[2], x.shape[3])
+        if ctx.needs_input_grad[1]:
+            dw = ext.gconv_wgrad(x, dy, ctx.stride, ctx.padding, ctx.groups,
+                                 not w.is_contiguous())
+        return dx, dw, None, None, None
+
+
+def _gconv_in_envelope(x, w, stride, padding, groups) -> bool:
+    """The cases gconv.hip implements: C_in == C_out == C, C % 32 == 0,
+    C / groups in {4, 8, 16, 32}, 3x3, stride 1|2, pad 0|1 (same for H and W),
+    dense weight in either layout, output non-empty."""
+    if x.dim() != 4 or w.dim() != 4 or not isinstance(stride, int) \
+            or not isinstance(padding, int) or not isinstance(groups, int):
+        return False
+    C = x.shape[1]
+    if groups <= 1 or C % groups != 0 or C % 32 != 0:
+        return False
+    Cg = C // groups
+    return (Cg in (4, 8, 16, 32) and tuple(w.shape) == (C, Cg, 3, 3)
+            and 0 < x.numel() < 2 ** 31
+            and stride in (1, 2) and padding in (0, 1)
+            and x.shape[2] + 2 * padding >= 3 and x.shape[3] + 2 * padding >= 3
+            and w.dtype == x.dtype
+            and (w.is_contiguous()
+                 or w.is_contiguous(memory_format=torch.channels_last))
+            and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
+
+
+def grouped_conv2d(x, w, stride: int = 1, padding: int = 0, groups: int = 1):
+    """Grouped conv: x (N,C,H,W), w (C_out, C/groups, k, k).
+
+    GPU bf16/fp16 3x3 cases inside the kernel envelope run the hand HIP
+    grouped kernels; everything else (CPU, fp32, other channel counts or
+    kernel sizes, C_in != C_out, DTMX_FALLBACK=gconv) is torch's grouped
+    conv. Depthwise (one channel per group) belongs to depthwise_conv2d."""
+    if _use_hip(x, w, op="gconv") and _gconv_in_envelope(x, w, stride, padding,
+                                                        groups):
+        x = x.contiguous(memory_format=torch.channels_last)
+        return _GroupedConvNHWC.apply(x, w, stride, padding, groups)
+    return F.conv2d(x, w, None, stride, padding, 1, groups)
 
 
 # --------------------------------------------------------------- batch norm

@@ -98,11 +98,12 @@ class GroupedConv2dNHWC(nn.Module):
     """Grouped / depthwise conv (mobilenet, resnext); groups==1 uses
     Conv2dNHWC instead. Depthwise (groups == in == out channels, mobilenet)
     goes through DF.depthwise_conv2d — the hand HIP depthwise 3x3 kernels
-    (dwconv.hip) on GPU bf16/fp16. Every other groups>1 case (resnext's
-    cardinality-32 3x3s) has no hand kernel yet — the implicit-GEMM convs
-    are dense-gather only — and routes through torch's conv on
-    channels_last memory (MIOpen on ROCm), the documented long-tail
-    substrate path."""
+    (dwconv.hip) on GPU bf16/fp16. Every other groups>1 case goes through
+    DF.grouped_conv2d: 3x3 with in == out channels and 4, 8, 16 or 32
+    channels per group (resnext's cardinality-32 3x3s) runs the hand HIP
+    MFMA kernels (gconv.hip) on GPU bf16/fp16, with the weight in either
+    dense layout; what is outside that envelope (other kernel sizes,
+    in != out channels, channel multipliers) is torch's grouped conv."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1,
                  padding=0, groups=1, bias=False):
@@ -119,16 +120,15 @@ class GroupedConv2dNHWC(nn.Module):
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
 
     def forward(self, x):
-        import torch.nn.functional as F
         if self.depthwise:
             y = DF.depthwise_conv2d(x, self.weight.to(x.dtype), self.stride,
                                     self.padding)
-            if self.bias is not None:
-                y = y + self.bias.reshape(1, -1, 1, 1).to(y.dtype)
-            return y
-        return F.conv2d(x, self.weight.to(x.dtype),
-                        self.bias.to(x.dtype) if self.bias is not None else None,
-                        self.stride, self.padding, 1, self.groups)
+        else:
+            y = DF.grouped_conv2d(x, self.weight.to(x.dtype), self.stride,
+                                  self.padding, self.groups)
+        if self.bias is not None:
+            y = y + self.bias.reshape(1, -1, 1, 1).to(y.dtype)
+        return y
 
 
 class ReLU(nn.Module):
