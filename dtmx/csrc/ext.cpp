@@ -25,6 +25,9 @@ at::Tensor gconv_fwd(const at::Tensor&, const at::Tensor&, long, long, long);
 at::Tensor gconv_dgrad(const at::Tensor&, const at::Tensor&, long, long, long, long,
                        long);
 at::Tensor gconv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, bool);
+// avgpool.hip
+at::Tensor avgpool_fwd(const at::Tensor&, long, long, long, bool);
+at::Tensor avgpool_bwd(const at::Tensor&, long, long, long, long, long, bool);
 // batchnorm.hip
 std::vector<at::Tensor> bn_fwd_train(const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, at::Tensor, at::Tensor,
@@ -137,6 +140,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd_dx_presummed", &dtmx::bn_bwd_dx_presummed);
   m.def("maxpool_fwd", &dtmx::maxpool_fwd);
   m.def("maxpool_bwd", &dtmx::maxpool_bwd);
+  m.def("avgpool_fwd", &dtmx::avgpool_fwd, py::arg("x"), py::arg("kernel"),
+        py::arg("stride"), py::arg("pad"), py::arg("count_include_pad"));
+  m.def("avgpool_bwd", &dtmx::avgpool_bwd, py::arg("dy"), py::arg("H"),
+        py::arg("W"), py::arg("kernel"), py::arg("stride"), py::arg("pad"),
+        py::arg("count_include_pad"));
   m.def("global_avgpool_fwd", &dtmx::global_avgpool_fwd);
   m.def("global_avgpool_bwd", &dtmx::global_avgpool_bwd);
   m.def("relu_fwd", &dtmx::relu_fwd);

@@ -7,10 +7,9 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
-from ..ops.layers import (BatchNorm2dNHWC, Conv2dNHWC, GlobalAvgPool,
-                          LinearBF16, MaxPool2dNHWC)
+from ..ops.layers import (AvgPool2dNHWC, BatchNorm2dNHWC, Conv2dNHWC,
+                          GlobalAvgPool, LinearBF16, MaxPool2dNHWC)
 
 
 class ConvBNRelu(nn.Module):
@@ -26,11 +25,6 @@ class ConvBNRelu(nn.Module):
         return self.bn(self.conv(x))
 
 
-class _AvgPool3s1(nn.Module):
-    def forward(self, x):
-        return F.avg_pool2d(x, 3, 1, 1, count_include_pad=True)
-
-
 class IncA(nn.Module):
     """InceptionFactoryA: 1x1 | 1x1->3x3 | 1x1->3x3->3x3 | pool->1x1."""
 
@@ -40,7 +34,8 @@ class IncA(nn.Module):
         self.b2 = nn.Sequential(ConvBNRelu(cin, n3r, 1), ConvBNRelu(n3r, n3, 3, 1, 1))
         self.b3 = nn.Sequential(ConvBNRelu(cin, d3r, 1), ConvBNRelu(d3r, d3, 3, 1, 1),
                                 ConvBNRelu(d3, d3, 3, 1, 1))
-        pool_l = _AvgPool3s1() if pool == "avg" else MaxPool2dNHWC(3, 1, 1)
+        pool_l = (AvgPool2dNHWC(3, 1, 1, count_include_pad=True) if pool == "avg"
+                  else MaxPool2dNHWC(3, 1, 1))
         self.b4 = nn.Sequential(pool_l, ConvBNRelu(cin, proj, 1))
         self.out_channels = n1 + n3 + d3 + proj
 

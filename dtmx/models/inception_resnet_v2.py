@@ -6,8 +6,8 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
+from ..ops import functional as DF
 from ..ops.layers import (BatchNorm2dNHWC, Conv2dNHWC, Dropout,
                           GlobalAvgPool, LinearBF16, MaxPool2dNHWC, ReLU)
 
@@ -40,7 +40,7 @@ class Stem(nn.Module):
 
     def forward(self, x):
         x = self.seq(x)
-        p = F.avg_pool2d(x, 3, 1, 1, count_include_pad=False)
+        p = DF.avg_pool2d(x, 3, 1, 1, count_include_pad=False)
         return torch.cat([self.b1(x), self.b2(x), self.b3(x), self.b4(p)], dim=1)
 
 

@@ -5,7 +5,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..ops.layers import BatchNorm2dNHWC, Conv2dNHWC, GlobalAvgPool, LinearBF16, MaxPool2dNHWC
+from ..ops.layers import (AvgPool2dNHWC, BatchNorm2dNHWC, Conv2dNHWC,
+                          GlobalAvgPool, LinearBF16, MaxPool2dNHWC)
 
 
 class ConvBN(nn.Module):
@@ -18,9 +19,8 @@ class ConvBN(nn.Module):
         return self.bn(self.conv(x))
 
 
-class _AvgPool3s1(nn.Module):
-    def forward(self, x):
-        return torch.nn.functional.avg_pool2d(x, 3, 1, 1, count_include_pad=False)
+def _AvgPool3s1():
+    return AvgPool2dNHWC(3, 1, 1, count_include_pad=False)
 
 
 class InceptionA(nn.Module):

@@ -7,9 +7,8 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
-from ..ops.layers import (BatchNorm2dNHWC, Conv2dNHWC, Dropout,
+from ..ops.layers import (AvgPool2dNHWC, BatchNorm2dNHWC, Conv2dNHWC, Dropout,
                           GlobalAvgPool, LinearBF16, MaxPool2dNHWC)
 
 
@@ -23,9 +22,8 @@ class ConvBN(nn.Module):
         return self.bn(self.conv(x))
 
 
-class _AvgPool3s1(nn.Module):
-    def forward(self, x):
-        return F.avg_pool2d(x, 3, 1, 1, count_include_pad=False)
+def _AvgPool3s1():
+    return AvgPool2dNHWC(3, 1, 1, count_include_pad=False)
 
 
 class Stem(nn.Module):

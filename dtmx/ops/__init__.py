@@ -4,6 +4,7 @@ from .layers import (  # noqa: F401
     BatchNorm2dNHWC,
     ReLU,
     MaxPool2dNHWC,
+    AvgPool2dNHWC,
     GlobalAvgPool,
     LinearBF16,
     AddRelu,

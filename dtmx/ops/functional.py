@@ -11,6 +11,7 @@ Reference kernel parity:
   grouped 3x3 conv       <- src/operator/nn/convolution.cu (num_group > 1)
   batch_norm fwd/bwd     <- src/operator/nn/batch_norm.cu:208-360
   pooling                <- src/operator/nn/pool.cuh
+  windowed avg pool      <- src/operator/nn/pool.cuh (avg, both pad conventions)
   relu / add(+relu)      <- mshadow_op elementwise kernels
   softmax+CE (fused)     <- src/operator/nn/softmax-inl.h:166-260, softmax_output
   linear                 <- fully_connected-inl.h (cuBLAS) -> dtmx MFMA GEMM
@@ -304,6 +305,54 @@ def max_pool2d(x, kernel: int, stride: int, padding: int = 0):
     if _use_hip(x, op="pool"):
         return _MaxPoolNHWC.apply(x, kernel, stride, padding)
     return F.max_pool2d(x, kernel, stride, padding)
+
+
+class _AvgPoolNHWC(torch.autograd.Function):
+    """Windowed average pool on the avgpool.hip kernels. Nothing is saved:
+    the backward recomputes each window's divisor from its position."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, stride, padding, count_include_pad):
+        ext = require_ext()
+        ctx.in_hw = (x.shape[2], x.shape[3])
+        ctx.params = (kernel, stride, padding, count_include_pad)
+        return ext.avgpool_fwd(x, kernel, stride, padding, count_include_pad)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = require_ext()
+        k, s, p, cip = ctx.params
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        return (ext.avgpool_bwd(dy, ctx.in_hw[0], ctx.in_hw[1], k, s, p, cip),
+                None, None, None, None)
+
+
+def _avgpool_in_envelope(x, kernel, stride, padding) -> bool:
+    """The cases avgpool.hip implements: square window 2..8, stride 1..8,
+    pad 0..kernel/2 (same for H and W, so plain ints only), floor output
+    size, C % 8 == 0, 0 < numel < 2^31, output non-empty."""
+    if x.dim() != 4 or not all(type(v) is int for v in (kernel, stride, padding)):
+        return False
+    return (2 <= kernel <= 8 and 1 <= stride <= 8 and 0 <= padding <= kernel // 2
+            and x.shape[1] % 8 == 0 and 0 < x.numel() < 2 ** 31
+            and x.shape[2] + 2 * padding >= kernel
+            and x.shape[3] + 2 * padding >= kernel
+            and x.data_ptr() % 16 == 0)
+
+
+def avg_pool2d(x, kernel, stride=None, padding=0, count_include_pad: bool = True):
+    """Windowed average pool, F.avg_pool2d's defaults and divisor semantics
+    (floor output size).
+
+    GPU bf16/fp16 cases inside the kernel envelope run the hand HIP kernels
+    (3x3 stride 1 pad 1, the Inception pool branch, on the separable strip
+    kernel); everything else (CPU, fp32, C % 8 != 0, tuple arguments,
+    DTMX_FALLBACK=avgpool) is exactly F.avg_pool2d."""
+    s = kernel if stride is None else stride
+    if _use_hip(x, op="avgpool") and _avgpool_in_envelope(x, kernel, s, padding):
+        x = x.contiguous(memory_format=torch.channels_last)
+        return _AvgPoolNHWC.apply(x, kernel, s, padding, bool(count_include_pad))
+    return F.avg_pool2d(x, kernel, stride, padding, False, count_include_pad)
 
 
 class _GlobalAvgPoolNHWC(torch.autograd.Function):

@@ -152,6 +152,28 @@ class MaxPool2dNHWC(nn.Module):
         return DF.max_pool2d(x, self.kernel_size, self.stride, self.padding)
 
 
+class AvgPool2dNHWC(nn.Module):
+    """Windowed average pool with nn.AvgPool2d's defaults (stride = kernel,
+    count_include_pad=True). GPU bf16/fp16 inside the avgpool.hip envelope
+    runs the hand HIP kernels; everything else is F.avg_pool2d."""
+
+    def __init__(self, kernel_size, stride=None, padding=0,
+                 count_include_pad=True):
+        super().__init__()
+        self.kernel_size = kernel_size
+        self.stride = stride
+        self.padding = padding
+        self.count_include_pad = count_include_pad
+
+    def forward(self, x):
+        return DF.avg_pool2d(x, self.kernel_size, self.stride, self.padding,
+                             self.count_include_pad)
+
+    def extra_repr(self):
+        return (f"k={self.kernel_size}, s={self.stride}, p={self.padding}, "
+                f"count_include_pad={self.count_include_pad}")
+
+
 class GlobalAvgPool(nn.Module):
     def forward(self, x):
         return DF.global_avg_pool(x)

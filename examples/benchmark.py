@@ -16,7 +16,7 @@ def run_one(n, args):
     passthru = ["--gpus", str(n), "--steps", str(args.steps),
                 "--warmup", str(args.warmup), "--batch-size", str(args.batch_size),
                 "--network", args.network, "--num-layers", str(args.num_layers),
-                "--dtype", args.dtype]
+                "--dtype", args.dtype, "--image-shape", args.image_shape]
     if n == 1:
         cmd = [sys.executable, bench] + passthru
     else:
@@ -40,6 +40,7 @@ if __name__ == "__main__":
     ap.add_argument("--network", type=str, default="resnet")
     ap.add_argument("--num-layers", type=int, default=50)
     ap.add_argument("--dtype", type=str, default="bfloat16")
+    ap.add_argument("--image-shape", type=str, default="3,224,224")
     args = ap.parse_args()
 
     base = None
