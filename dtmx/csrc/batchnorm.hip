@@ -322,12 +322,25 @@ __global__ void bn_infer_prep_kernel(const elem_t* __restrict__ gamma,
   shift[c] = (float)beta[c] - running_mean[c] * g * invstd;
 }
 
+// packed relu mask of one stored V8 of y: bit e = !(y[e] <= 0), evaluated on
+// the converted elem_t value, i.e. exactly the predicate the backward kernels
+// apply to y (NaN keeps the gradient, fp16 underflow to 0 drops it).
+template <typename V8>
+__device__ __forceinline__ uint8_t relu_mask8(V8 o) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) m |= (uint32_t)(!((float)o[e] <= 0.f)) << e;
+  return (uint8_t)m;
+}
+
 // ---- apply: y = x*scale + shift (+relu), V8, 32-bit indexing ---------
-template <typename elem_t>
+// MASK: also store the packed relu mask byte [rows][C/8] of each V8 written.
+template <typename elem_t, bool MASK>
 __global__ void bn_apply_kernel(const elem_t* __restrict__ x, elem_t* __restrict__ y,
                                 const float* __restrict__ scale,
                                 const float* __restrict__ shift,
                                 const elem_t* __restrict__ residual,  // nullable
+                                uint8_t* __restrict__ mask,  // MASK only
                                 uint32_t total8, FastDiv dcv, int relu) {
   using V8 = typename E8<elem_t>::v8;
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -344,6 +357,7 @@ __global__ void bn_apply_kernel(const elem_t* __restrict__ x, elem_t* __restrict
       o[e] = (elem_t)r;
     }
     *(V8*)(y + (size_t)ii * 8) = o;
+    if constexpr (MASK) mask[ii] = relu_mask8(o);
   };
   V8 zed = {};
   // 2x unrolled so 2-4 16-B loads are in flight per wave (single-chunk loop
@@ -364,10 +378,14 @@ __global__ void bn_apply_kernel(const elem_t* __restrict__ x, elem_t* __restrict
 }
 
 // ---- backward stats: per-channel sum(dy), sum(dy*xhat), vectorized -------
-template <typename elem_t>
+// MASK: the relu mask is the packed byte `mask`, not y (compile-time, so the
+// y form keeps its registers and occupancy)
+template <typename elem_t, bool MASK>
 __global__ void bn_bwd_stats_kernel(const elem_t* __restrict__ x,
                                     const elem_t* __restrict__ dy,
                                     const elem_t* __restrict__ y,  // relu mask
+                                    const uint8_t* __restrict__ mask,  // MASK only:
+                                    // packed relu mask [rows][cvecs]
                                     const float* __restrict__ save_mean,
                                     const float* __restrict__ save_invstd,
                                     float* __restrict__ pdb, float* __restrict__ pdg,
@@ -388,11 +406,12 @@ __global__ void bn_bwd_stats_kernel(const elem_t* __restrict__ x,
     invstd[e] = cv_ok ? save_invstd[cv * 8 + e] : 0.f;
   }
   float db[8] = {}, dg[8] = {};
-  auto accum = [&](V8 xv, V8 gv, V8 yv) {
+  const bool rely = relu && !MASK, relm = relu && MASK;  // mask source
+  auto accum = [&](V8 xv, V8 gv, V8 yv, uint32_t mb) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float g = (float)gv[e];
-      if (relu && (float)yv[e] <= 0.f) g = 0.f;
+      if (relu && (MASK ? !((mb >> e) & 1) : (float)yv[e] <= 0.f)) g = 0.f;
       db[e] += g;
       dg[e] += g * ((float)xv[e] - mean[e]) * invstd[e];
     }
@@ -403,15 +422,16 @@ __global__ void bn_bwd_stats_kernel(const elem_t* __restrict__ x,
     size_t o0 = (size_t)r * C + cv * 8, o1 = (size_t)(r + rstep) * C + cv * 8;
     V8 x0 = *(const V8*)(x + o0), x1 = *(const V8*)(x + o1);
     V8 g0 = *(const V8*)(dy + o0), g1 = *(const V8*)(dy + o1);
-    V8 y0 = relu ? *(const V8*)(y + o0) : zed;
-    V8 y1 = relu ? *(const V8*)(y + o1) : zed;
-    accum(x0, g0, y0);
-    accum(x1, g1, y1);
+    V8 y0 = rely ? *(const V8*)(y + o0) : zed;
+    V8 y1 = rely ? *(const V8*)(y + o1) : zed;
+    uint32_t m0 = relm ? mask[o0 >> 3] : 0, m1 = relm ? mask[o1 >> 3] : 0;
+    accum(x0, g0, y0, m0);
+    accum(x1, g1, y1, m1);
   }
   for (; r < r1; r += rstep) {
     size_t o0 = (size_t)r * C + cv * 8;
     accum(*(const V8*)(x + o0), *(const V8*)(dy + o0),
-          relu ? *(const V8*)(y + o0) : zed);
+          rely ? *(const V8*)(y + o0) : zed, relm ? mask[o0 >> 3] : 0);
   }
   __shared__ float red[256 * 8];
   block_col_reduce(red, db, cv, cpb, cvecs, pdb + (size_t)blockIdx.y * C);
@@ -441,10 +461,13 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ pdb,
 }
 
 // dx = gamma*invstd * (dy - dbeta/M - xhat * dgamma/M)
-template <typename elem_t>
+// MASK: the relu mask is the packed byte `mask`, not y (compile-time, so the
+// y form keeps its registers and occupancy)
+template <typename elem_t, bool MASK>
 __global__ void bn_bwd_dx_kernel(const elem_t* __restrict__ x,
                                  const elem_t* __restrict__ dy,
                                  const elem_t* __restrict__ y,
+                                 const uint8_t* __restrict__ mask,  // MASK only
                                  const float* __restrict__ save_mean,
                                  const float* __restrict__ save_invstd,
                                  const elem_t* __restrict__ gamma,
@@ -457,7 +480,8 @@ __global__ void bn_bwd_dx_kernel(const elem_t* __restrict__ x,
   using V8 = typename E8<elem_t>::v8;
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t stride = gridDim.x * blockDim.x;
-  auto body = [&](uint32_t ii, V8 xv, V8 gv, V8 yv) {
+  const bool rely = relu && !MASK, relm = relu && MASK;  // mask source
+  auto body = [&](uint32_t ii, V8 xv, V8 gv, V8 yv, uint32_t mb) {
     uint32_t q = dcv.div(ii);
     uint32_t c0 = dcv.mod(ii, q) * 8;
     size_t off = (size_t)ii * 8;
@@ -466,7 +490,7 @@ __global__ void bn_bwd_dx_kernel(const elem_t* __restrict__ x,
     for (int e = 0; e < 8; ++e) {
       uint32_t c = c0 + e;
       float g = (float)gv[e];
-      if (relu && (float)yv[e] <= 0.f) g = 0.f;
+      if (relu && (MASK ? !((mb >> e) & 1) : (float)yv[e] <= 0.f)) g = 0.f;
       if (dres) om[e] = (elem_t)g;
       float invstd = save_invstd[c];
       float xh = ((float)xv[e] - save_mean[c]) * invstd;
@@ -482,15 +506,16 @@ __global__ void bn_bwd_dx_kernel(const elem_t* __restrict__ x,
     size_t o0 = (size_t)i * 8, o1 = (size_t)(i + stride) * 8;
     V8 x0 = *(const V8*)(x + o0), x1 = *(const V8*)(x + o1);
     V8 g0 = *(const V8*)(dy + o0), g1 = *(const V8*)(dy + o1);
-    V8 y0 = relu ? *(const V8*)(y + o0) : zed;
-    V8 y1 = relu ? *(const V8*)(y + o1) : zed;
-    body(i, x0, g0, y0);
-    body(i + stride, x1, g1, y1);
+    V8 y0 = rely ? *(const V8*)(y + o0) : zed;
+    V8 y1 = rely ? *(const V8*)(y + o1) : zed;
+    uint32_t m0 = relm ? mask[i] : 0, m1 = relm ? mask[i + stride] : 0;
+    body(i, x0, g0, y0, m0);
+    body(i + stride, x1, g1, y1, m1);
   }
   for (; i < total8; i += stride) {
     size_t o0 = (size_t)i * 8;
     body(i, *(const V8*)(x + o0), *(const V8*)(dy + o0),
-         relu ? *(const V8*)(y + o0) : zed);
+         rely ? *(const V8*)(y + o0) : zed, relm ? mask[i] : 0);
   }
 }
 
@@ -519,10 +544,13 @@ __global__ void bn_dx_coef_kernel(const float* __restrict__ tdb,
   kb[c] = -a * tdb[c] * inv_count - cc * save_mean[c];
 }
 
-template <typename elem_t>
+// MASK: the relu mask is the packed byte `mask`, not y (compile-time, so the
+// y form keeps its registers and occupancy)
+template <typename elem_t, bool MASK>
 __global__ void bn_bwd_dx_coef_kernel(const elem_t* __restrict__ x,
                                       const elem_t* __restrict__ dy,
                                       const elem_t* __restrict__ y,
+                                      const uint8_t* __restrict__ mask,  // MASK only
                                       const float* __restrict__ ka,
                                       const float* __restrict__ kb,
                                       const float* __restrict__ kc,
@@ -532,7 +560,8 @@ __global__ void bn_bwd_dx_coef_kernel(const elem_t* __restrict__ x,
   using V8 = typename E8<elem_t>::v8;
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t stride = gridDim.x * blockDim.x;
-  auto body = [&](uint32_t ii, V8 xv, V8 gv, V8 yv) {
+  const bool rely = relu && !MASK, relm = relu && MASK;  // mask source
+  auto body = [&](uint32_t ii, V8 xv, V8 gv, V8 yv, uint32_t mb) {
     uint32_t q = dcv.div(ii);
     uint32_t c0 = dcv.mod(ii, q) * 8;
     size_t off = (size_t)ii * 8;
@@ -541,7 +570,7 @@ __global__ void bn_bwd_dx_coef_kernel(const elem_t* __restrict__ x,
     for (int e = 0; e < 8; ++e) {
       uint32_t c = c0 + e;
       float g = (float)gv[e];
-      if (relu && (float)yv[e] <= 0.f) g = 0.f;
+      if (relu && (MASK ? !((mb >> e) & 1) : (float)yv[e] <= 0.f)) g = 0.f;
       if (dres) om[e] = (elem_t)g;
       o[e] = (elem_t)(ka[c] * g + kc[c] * (float)xv[e] + kb[c]);
     }
@@ -553,15 +582,16 @@ __global__ void bn_bwd_dx_coef_kernel(const elem_t* __restrict__ x,
     size_t o0 = (size_t)i * 8, o1 = (size_t)(i + stride) * 8;
     V8 x0 = *(const V8*)(x + o0), x1 = *(const V8*)(x + o1);
     V8 g0 = *(const V8*)(dy + o0), g1 = *(const V8*)(dy + o1);
-    V8 y0 = relu ? *(const V8*)(y + o0) : zed;
-    V8 y1 = relu ? *(const V8*)(y + o1) : zed;
-    body(i, x0, g0, y0);
-    body(i + stride, x1, g1, y1);
+    V8 y0 = rely ? *(const V8*)(y + o0) : zed;
+    V8 y1 = rely ? *(const V8*)(y + o1) : zed;
+    uint32_t m0 = relm ? mask[i] : 0, m1 = relm ? mask[i + stride] : 0;
+    body(i, x0, g0, y0, m0);
+    body(i + stride, x1, g1, y1, m1);
   }
   for (; i < total8; i += stride) {
     size_t o0 = (size_t)i * 8;
     body(i, *(const V8*)(x + o0), *(const V8*)(dy + o0),
-         relu ? *(const V8*)(y + o0) : zed);
+         rely ? *(const V8*)(y + o0) : zed, relm ? mask[i] : 0);
   }
 }
 
@@ -572,12 +602,13 @@ __global__ void bn_bwd_dx_coef_kernel(const elem_t* __restrict__ x,
 // Owning a fixed cv per thread hoists the tables into registers before the
 // row loop; coalescing stays intact (cpb consecutive lanes cover cpb*16 B
 // of one row). Geometry = bn_stats_kernel's (cv, strided rows).
-template <typename elem_t>
+template <typename elem_t, bool MASK>
 __global__ void bn_apply_col_kernel(const elem_t* __restrict__ x,
                                     elem_t* __restrict__ y,
                                     const float* __restrict__ scale,
                                     const float* __restrict__ shift,
                                     const elem_t* __restrict__ residual,
+                                    uint8_t* __restrict__ mask,  // MASK only
                                     uint32_t rows, uint32_t cvecs, uint32_t cpb,
                                     uint32_t rows_per_block, int relu) {
   using V8 = typename E8<elem_t>::v8;
@@ -603,6 +634,7 @@ __global__ void bn_apply_col_kernel(const elem_t* __restrict__ x,
       o[e] = (elem_t)r;
     }
     *(V8*)(y + off) = o;
+    if constexpr (MASK) mask[off >> 3] = relu_mask8(o);
   };
   V8 zed = {};
   uint32_t r = r0;
@@ -622,10 +654,13 @@ __global__ void bn_apply_col_kernel(const elem_t* __restrict__ x,
   }
 }
 
-template <typename elem_t>
+// MASK: the relu mask is the packed byte `mask`, not y (compile-time, so the
+// y form keeps its registers and occupancy)
+template <typename elem_t, bool MASK>
 __global__ void bn_bwd_dx_col_kernel(const elem_t* __restrict__ x,
                                      const elem_t* __restrict__ dy,
                                      const elem_t* __restrict__ y,
+                                     const uint8_t* __restrict__ mask,  // MASK only
                                      const float* __restrict__ ka,
                                      const float* __restrict__ kb,
                                      const float* __restrict__ kc,
@@ -648,12 +683,13 @@ __global__ void bn_bwd_dx_col_kernel(const elem_t* __restrict__ x,
     b8[e] = kb[cv * 8 + e];
     c8[e] = kc[cv * 8 + e];
   }
-  auto body = [&](size_t off, V8 xv, V8 gv, V8 yv) {
+  const bool rely = relu && !MASK, relm = relu && MASK;  // mask source
+  auto body = [&](size_t off, V8 xv, V8 gv, V8 yv, uint32_t mb) {
     V8 o, om;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float g = (float)gv[e];
-      if (relu && (float)yv[e] <= 0.f) g = 0.f;
+      if (relu && (MASK ? !((mb >> e) & 1) : (float)yv[e] <= 0.f)) g = 0.f;
       if (dres) om[e] = (elem_t)g;
       o[e] = (elem_t)(a8[e] * g + c8[e] * (float)xv[e] + b8[e]);
     }
@@ -667,15 +703,16 @@ __global__ void bn_bwd_dx_col_kernel(const elem_t* __restrict__ x,
     size_t o1 = ((size_t)(r + rstep) * cvecs + cv) * 8;
     V8 x0 = *(const V8*)(x + o0), x1 = *(const V8*)(x + o1);
     V8 g0 = *(const V8*)(dy + o0), g1 = *(const V8*)(dy + o1);
-    V8 y0 = relu ? *(const V8*)(y + o0) : zed;
-    V8 y1 = relu ? *(const V8*)(y + o1) : zed;
-    body(o0, x0, g0, y0);
-    body(o1, x1, g1, y1);
+    V8 y0 = rely ? *(const V8*)(y + o0) : zed;
+    V8 y1 = rely ? *(const V8*)(y + o1) : zed;
+    uint32_t m0 = relm ? mask[o0 >> 3] : 0, m1 = relm ? mask[o1 >> 3] : 0;
+    body(o0, x0, g0, y0, m0);
+    body(o1, x1, g1, y1, m1);
   }
   for (; r < r1; r += rstep) {
     size_t o0 = ((size_t)r * cvecs + cv) * 8;
     body(o0, *(const V8*)(x + o0), *(const V8*)(dy + o0),
-         relu ? *(const V8*)(y + o0) : zed);
+         rely ? *(const V8*)(y + o0) : zed, relm ? mask[o0 >> 3] : 0);
   }
 }
 
@@ -698,6 +735,22 @@ static void bn_check_vec(const at::Tensor& x, const at::Tensor& v,
                          const char* name) {
   TORCH_CHECK(v.numel() == x.size(1) && v.is_contiguous(), "bn: ", name,
               " must be a contiguous vector of C elements");
+}
+
+// packed relu mask argument (bn_fwd_train's 4th output): uint8 [rows][C/8]
+// on x's device, dense. Returns nullptr when absent.
+static const uint8_t* bn_check_mask(const at::Tensor& x,
+                                    const c10::optional<at::Tensor>& mask,
+                                    bool fuse_relu) {
+  if (!mask.has_value() || !mask->defined()) return nullptr;
+  TORCH_CHECK(fuse_relu, "bn: a relu mask needs fuse_relu");
+  const long rows = x.size(0) * x.size(2) * x.size(3);
+  TORCH_CHECK(mask->scalar_type() == at::kByte && mask->device() == x.device() &&
+                  mask->dim() == 2 && mask->size(0) == rows &&
+                  mask->size(1) == x.size(1) / 8 && mask->is_contiguous(),
+              "bn: mask must be a contiguous uint8 [N*H*W][C/8] tensor on the "
+              "device of x");
+  return mask->data_ptr<uint8_t>();
 }
 
 static bool bn_col_on() {
@@ -744,27 +797,36 @@ template <typename elem_t>
 static void launch_bn_apply(const elem_t* x, elem_t* y, const float* scale,
                             const float* shift, const elem_t* residual,
                             uint32_t rows, uint32_t cvecs, int relu,
-                            hipStream_t s) {
+                            hipStream_t s, uint8_t* mask = nullptr) {
   if (bn_col_on()) {
     uint32_t cpb = bn_cpb(cvecs);
     dim3 grid;
     uint32_t rpb;
     bn_grid(rows, cvecs, cpb, grid, rpb);
-    bn_apply_col_kernel<<<grid, 256, 0, s>>>(x, y, scale, shift, residual,
-                                             rows, cvecs, cpb, rpb, relu);
+    if (mask)
+      bn_apply_col_kernel<elem_t, true><<<grid, 256, 0, s>>>(
+          x, y, scale, shift, residual, mask, rows, cvecs, cpb, rpb, relu);
+    else
+      bn_apply_col_kernel<elem_t, false><<<grid, 256, 0, s>>>(
+          x, y, scale, shift, residual, nullptr, rows, cvecs, cpb, rpb, relu);
   } else {
     uint32_t total8 = rows * cvecs;
     FastDiv dcv;
     dcv.init(cvecs);
     uint32_t blocks = std::min<uint32_t>((total8 + 255) / 256, 2048);
-    bn_apply_kernel<<<blocks, 256, 0, s>>>(x, y, scale, shift, residual,
-                                           total8, dcv, relu);
+    if (mask)
+      bn_apply_kernel<elem_t, true><<<blocks, 256, 0, s>>>(
+          x, y, scale, shift, residual, mask, total8, dcv, relu);
+    else
+      bn_apply_kernel<elem_t, false><<<blocks, 256, 0, s>>>(
+          x, y, scale, shift, residual, nullptr, total8, dcv, relu);
   }
 }
 
 template <typename elem_t>
 static void launch_bn_dx_coef(const elem_t* x, const elem_t* dy,
-                              const elem_t* y, const float* ka,
+                              const elem_t* y, const uint8_t* mask,
+                              const float* ka,
                               const float* kb, const float* kc, elem_t* dx,
                               elem_t* dres, uint32_t rows, uint32_t cvecs,
                               int relu, hipStream_t s) {
@@ -773,15 +835,19 @@ static void launch_bn_dx_coef(const elem_t* x, const elem_t* dy,
     dim3 grid;
     uint32_t rpb;
     bn_grid(rows, cvecs, cpb, grid, rpb);
-    bn_bwd_dx_col_kernel<<<grid, 256, 0, s>>>(x, dy, y, ka, kb, kc, dx, dres,
-                                              rows, cvecs, cpb, rpb, relu);
+    auto k = mask ? bn_bwd_dx_col_kernel<elem_t, true>
+                  : bn_bwd_dx_col_kernel<elem_t, false>;
+    k<<<grid, 256, 0, s>>>(x, dy, y, mask, ka, kb, kc, dx, dres, rows, cvecs,
+                           cpb, rpb, relu);
   } else {
     uint32_t total8 = rows * cvecs;
     FastDiv dcv;
     dcv.init(cvecs);
     uint32_t blocks = std::min<uint32_t>((total8 + 255) / 256, 2048);
-    bn_bwd_dx_coef_kernel<<<blocks, 256, 0, s>>>(x, dy, y, ka, kb, kc, dx,
-                                                 dres, total8, dcv, relu);
+    auto k = mask ? bn_bwd_dx_coef_kernel<elem_t, true>
+                  : bn_bwd_dx_coef_kernel<elem_t, false>;
+    k<<<blocks, 256, 0, s>>>(x, dy, y, mask, ka, kb, kc, dx, dres, total8, dcv,
+                             relu);
   }
 }
 
@@ -791,10 +857,12 @@ std::vector<at::Tensor> bn_fwd_train(const at::Tensor& x, const at::Tensor& gamm
                                      double eps, bool fuse_relu,
                                      const c10::optional<at::Tensor>& residual,
                                      const c10::optional<at::Tensor>& pre_psum,
-                                     const c10::optional<at::Tensor>& pre_psumsq) {
+                                     const c10::optional<at::Tensor>& pre_psumsq,
+                                     bool want_mask) {
   TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), "bn: x must be NHWC");
   uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   TORCH_CHECK(C % 8 == 0, "bn: C must be a multiple of 8, got ", C);
+  TORCH_CHECK(!want_mask || fuse_relu, "bn: want_mask needs fuse_relu");
   uint32_t rows = N * H * W, cvecs = C / 8;
   uint32_t cpb = bn_cpb(cvecs);
   auto opt_f = x.options().dtype(at::kFloat);
@@ -829,6 +897,9 @@ std::vector<at::Tensor> bn_fwd_train(const at::Tensor& x, const at::Tensor& gamm
   auto save_mean = at::empty({(long)C}, opt_f), save_invstd = at::empty({(long)C}, opt_f);
   auto scale = at::empty({(long)C}, opt_f), shift = at::empty({(long)C}, opt_f);
   auto y = at::empty_like(x);
+  at::Tensor mask;  // packed relu mask, one byte per V8 of y
+  if (want_mask)
+    mask = at::empty({(long)rows, (long)cvecs}, x.options().dtype(at::kByte));
   auto s = bn_stream();
   DTMX_DISPATCH_16(x.scalar_type(), "bn_fwd", {
     if (!have_pre)
@@ -848,8 +919,10 @@ std::vector<at::Tensor> bn_fwd_train(const at::Tensor& x, const at::Tensor& gamm
         (const elem_t*)x.data_ptr(), (elem_t*)y.data_ptr(),
         scale.data_ptr<float>(), shift.data_ptr<float>(),
         residual.has_value() ? (const elem_t*)residual->data_ptr() : nullptr,
-        rows, cvecs, fuse_relu ? 1 : 0, s);
+        rows, cvecs, fuse_relu ? 1 : 0, s,
+        want_mask ? mask.data_ptr<uint8_t>() : nullptr);
   });
+  if (want_mask) return {y, save_mean, save_invstd, mask};
   return {y, save_mean, save_invstd};
 }
 
@@ -882,10 +955,14 @@ at::Tensor bn_fwd_infer(const at::Tensor& x, const at::Tensor& gamma,
 std::vector<at::Tensor> bn_bwd(const at::Tensor& x, const at::Tensor& dy,
                                const at::Tensor& gamma, const at::Tensor& save_mean,
                                const at::Tensor& save_invstd, bool fuse_relu,
-                               const at::Tensor& y, bool want_dres) {
+                               const at::Tensor& y, bool want_dres,
+                               const c10::optional<at::Tensor>& mask) {
   bn_check_x(x);
   bn_check_like(x, dy, "dy");
-  if (fuse_relu) bn_check_like(x, y, "y");  // y is only read as the relu mask
+  // y is only read as the relu mask; a packed mask replaces it (y is then
+  // neither checked nor touched)
+  const uint8_t* mk = bn_check_mask(x, mask, fuse_relu);
+  if (fuse_relu && !mk) bn_check_like(x, y, "y");
   bn_check_vec(x, save_mean, "save_mean");
   bn_check_vec(x, save_invstd, "save_invstd");
   uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
@@ -906,9 +983,12 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x, const at::Tensor& dy,
   if (want_dres) dres = at::empty_like(x);
   auto s = bn_stream();
   DTMX_DISPATCH_16(x.scalar_type(), "bn_bwd", {
-    bn_bwd_stats_kernel<<<grid, 256, 0, s>>>(
+    auto kstats = mk ? bn_bwd_stats_kernel<elem_t, true>
+                     : bn_bwd_stats_kernel<elem_t, false>;
+    kstats<<<grid, 256, 0, s>>>(
         (const elem_t*)x.data_ptr(), (const elem_t*)dy.data_ptr(),
-        (const elem_t*)y.data_ptr(), save_mean.data_ptr<float>(),
+        mk ? nullptr : (const elem_t*)y.data_ptr(), mk,
+        save_mean.data_ptr<float>(),
         save_invstd.data_ptr<float>(), pdb.data_ptr<float>(),
         pdg.data_ptr<float>(), rows, cvecs, cpb, rpb, fuse_relu ? 1 : 0);
     uint32_t ncv = std::min(cpb, 8u);
@@ -930,14 +1010,17 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x, const at::Tensor& dy,
           kb.data_ptr<float>(), kc.data_ptr<float>(), C, 1.f / rows);
       launch_bn_dx_coef<elem_t>(
           (const elem_t*)x.data_ptr(), (const elem_t*)dy.data_ptr(),
-          (const elem_t*)y.data_ptr(), ka.data_ptr<float>(),
+          mk ? nullptr : (const elem_t*)y.data_ptr(), mk, ka.data_ptr<float>(),
           kb.data_ptr<float>(), kc.data_ptr<float>(), (elem_t*)dx.data_ptr(),
           want_dres ? (elem_t*)dres.data_ptr() : nullptr, rows, cvecs,
           fuse_relu ? 1 : 0, s);
     } else {
-      bn_bwd_dx_kernel<<<blocks, 256, 0, s>>>(
+      auto kdx = mk ? bn_bwd_dx_kernel<elem_t, true>
+                    : bn_bwd_dx_kernel<elem_t, false>;
+      kdx<<<blocks, 256, 0, s>>>(
           (const elem_t*)x.data_ptr(), (const elem_t*)dy.data_ptr(),
-          (const elem_t*)y.data_ptr(), save_mean.data_ptr<float>(),
+          mk ? nullptr : (const elem_t*)y.data_ptr(), mk,
+          save_mean.data_ptr<float>(),
           save_invstd.data_ptr<float>(), (const elem_t*)gamma.data_ptr(),
           tdb.data_ptr<float>(), tdg.data_ptr<float>(), (elem_t*)dx.data_ptr(),
           want_dres ? (elem_t*)dres.data_ptr() : nullptr, total8, dcv,
@@ -1100,9 +1183,10 @@ std::vector<at::Tensor> bn_bwd_sums(const at::Tensor& x, const at::Tensor& dy,
   auto tdb = at::empty({(long)C}, opt_f), tdg = at::empty({(long)C}, opt_f);
   auto s = bn_stream();
   DTMX_DISPATCH_16(x.scalar_type(), "bn_bwd_sums", {
-    bn_bwd_stats_kernel<<<grid, 256, 0, s>>>(
+    bn_bwd_stats_kernel<elem_t, false><<<grid, 256, 0, s>>>(
         (const elem_t*)x.data_ptr(), (const elem_t*)dy.data_ptr(),
-        (const elem_t*)y.data_ptr(), save_mean.data_ptr<float>(),
+        (const elem_t*)y.data_ptr(), /*mask=*/nullptr,
+        save_mean.data_ptr<float>(),
         save_invstd.data_ptr<float>(), pdb.data_ptr<float>(),
         pdg.data_ptr<float>(), rows, cvecs, cpb, rpb, fuse_relu ? 1 : 0);
   });
@@ -1117,10 +1201,13 @@ std::vector<at::Tensor> bn_bwd_dx_presummed(
     const at::Tensor& x, const at::Tensor& dy, const at::Tensor& y,
     const at::Tensor& save_mean, const at::Tensor& save_invstd,
     const at::Tensor& gamma, const at::Tensor& tdb, const at::Tensor& tdg,
-    long count, bool fuse_relu, bool want_dres) {
+    long count, bool fuse_relu, bool want_dres,
+    const c10::optional<at::Tensor>& mask) {
   bn_check_x(x);
   bn_check_like(x, dy, "dy");
-  if (fuse_relu) bn_check_like(x, y, "y");  // y is only read as the relu mask
+  // y is only read as the relu mask; a packed mask replaces it
+  const uint8_t* mk = bn_check_mask(x, mask, fuse_relu);
+  if (fuse_relu && !mk) bn_check_like(x, y, "y");
   bn_check_vec(x, save_mean, "save_mean");
   bn_check_vec(x, save_invstd, "save_invstd");
   bn_check_vec(x, tdb, "tdb");
@@ -1148,14 +1235,17 @@ std::vector<at::Tensor> bn_bwd_dx_presummed(
           kb.data_ptr<float>(), kc.data_ptr<float>(), C, 1.f / (float)count);
       launch_bn_dx_coef<elem_t>(
           (const elem_t*)x.data_ptr(), (const elem_t*)dy.data_ptr(),
-          (const elem_t*)y.data_ptr(), ka.data_ptr<float>(),
+          mk ? nullptr : (const elem_t*)y.data_ptr(), mk, ka.data_ptr<float>(),
           kb.data_ptr<float>(), kc.data_ptr<float>(), (elem_t*)dx.data_ptr(),
           want_dres ? (elem_t*)dres.data_ptr() : nullptr, N * H * W, cvecs,
           fuse_relu ? 1 : 0, s);
     } else {
-      bn_bwd_dx_kernel<<<blocks, 256, 0, s>>>(
+      auto kdx = mk ? bn_bwd_dx_kernel<elem_t, true>
+                    : bn_bwd_dx_kernel<elem_t, false>;
+      kdx<<<blocks, 256, 0, s>>>(
           (const elem_t*)x.data_ptr(), (const elem_t*)dy.data_ptr(),
-          (const elem_t*)y.data_ptr(), save_mean.data_ptr<float>(),
+          mk ? nullptr : (const elem_t*)y.data_ptr(), mk,
+          save_mean.data_ptr<float>(),
           save_invstd.data_ptr<float>(), (const elem_t*)gamma.data_ptr(),
           tdb.data_ptr<float>(), tdg.data_ptr<float>(), (elem_t*)dx.data_ptr(),
           want_dres ? (elem_t*)dres.data_ptr() : nullptr, total8, dcv,

@@ -14,7 +14,8 @@ std::vector<at::Tensor> conv_dgrad_bnfuse(const at::Tensor&, const at::Tensor&,
                                           long, long, long, long,
                                           const c10::optional<at::Tensor>&,
                                           const at::Tensor&, const at::Tensor&,
-                                          const at::Tensor&, const at::Tensor&);
+                                          const at::Tensor&, const at::Tensor&,
+                                          const c10::optional<at::Tensor>&);
 std::vector<std::tuple<long, long, double>> wgrad_ws_stats();
 // dwconv.hip
 at::Tensor dwconv_fwd(const at::Tensor&, const at::Tensor&, long, long);
@@ -34,7 +35,7 @@ std::vector<at::Tensor> bn_fwd_train(const at::Tensor&, const at::Tensor&,
                                      double, double, bool,
                                      const c10::optional<at::Tensor>&,
                                      const c10::optional<at::Tensor>&,
-                                     const c10::optional<at::Tensor>&);
+                                     const c10::optional<at::Tensor>&, bool);
 std::vector<at::Tensor> conv_fwd_stats(const at::Tensor&, const at::Tensor&,
                                        long, long);
 std::vector<at::Tensor> bn_local_sums(const at::Tensor&);
@@ -53,13 +54,15 @@ std::vector<at::Tensor> bn_bwd_dx_presummed(const at::Tensor&, const at::Tensor&
                                             const at::Tensor&, const at::Tensor&,
                                             const at::Tensor&, const at::Tensor&,
                                             const at::Tensor&, const at::Tensor&,
-                                            long, bool, bool);
+                                            long, bool, bool,
+                                            const c10::optional<at::Tensor>&);
 at::Tensor bn_fwd_infer(const at::Tensor&, const at::Tensor&, const at::Tensor&,
                         const at::Tensor&, const at::Tensor&, double, bool,
                         const c10::optional<at::Tensor>&);
 std::vector<at::Tensor> bn_bwd(const at::Tensor&, const at::Tensor&,
                                const at::Tensor&, const at::Tensor&,
-                               const at::Tensor&, bool, const at::Tensor&, bool);
+                               const at::Tensor&, bool, const at::Tensor&, bool,
+                               const c10::optional<at::Tensor>&);
 // pool_elem.hip
 std::vector<at::Tensor> maxpool_fwd(const at::Tensor&, long, long, long);
 at::Tensor maxpool_bwd(const at::Tensor&, const at::Tensor&, long, long, long,
@@ -128,16 +131,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_dgrad_bnfuse", &dtmx::conv_dgrad_bnfuse, py::arg("dy"),
         py::arg("w"), py::arg("stride"), py::arg("pad"), py::arg("H"),
         py::arg("W"), py::arg("acc"), py::arg("y"), py::arg("xin"),
-        py::arg("mean"), py::arg("invstd"));
+        py::arg("mean"), py::arg("invstd"), py::arg("mask") = py::none());
   m.def("bn_bwd_finalize_slabs", &dtmx::bn_bwd_finalize_slabs);
   m.def("wgrad_ws_stats", &dtmx::wgrad_ws_stats);
-  m.def("bn_fwd_train", &dtmx::bn_fwd_train);
+  // want_mask appends a 4th output: the packed relu mask, uint8
+  // [N*H*W][C/8], bit e of byte (row, cv) = !(y[row][cv*8+e] <= 0). The
+  // backward entries take it as `mask` in place of their y operand.
+  m.def("bn_fwd_train", &dtmx::bn_fwd_train, py::arg("x"), py::arg("gamma"),
+        py::arg("beta"), py::arg("running_mean"), py::arg("running_var"),
+        py::arg("momentum"), py::arg("eps"), py::arg("fuse_relu"),
+        py::arg("residual"), py::arg("pre_psum"), py::arg("pre_psumsq"),
+        py::arg("want_mask") = false);
   m.def("bn_fwd_infer", &dtmx::bn_fwd_infer);
-  m.def("bn_bwd", &dtmx::bn_bwd);
+  m.def("bn_bwd", &dtmx::bn_bwd, py::arg("x"), py::arg("dy"), py::arg("gamma"),
+        py::arg("save_mean"), py::arg("save_invstd"), py::arg("fuse_relu"),
+        py::arg("y"), py::arg("want_dres"), py::arg("mask") = py::none());
   m.def("bn_local_sums", &dtmx::bn_local_sums);
   m.def("bn_fwd_presummed", &dtmx::bn_fwd_presummed);
   m.def("bn_bwd_sums", &dtmx::bn_bwd_sums);
-  m.def("bn_bwd_dx_presummed", &dtmx::bn_bwd_dx_presummed);
+  m.def("bn_bwd_dx_presummed", &dtmx::bn_bwd_dx_presummed, py::arg("x"),
+        py::arg("dy"), py::arg("y"), py::arg("save_mean"),
+        py::arg("save_invstd"), py::arg("gamma"), py::arg("tdb"),
+        py::arg("tdg"), py::arg("count"), py::arg("fuse_relu"),
+        py::arg("want_dres"), py::arg("mask") = py::none());
   m.def("maxpool_fwd", &dtmx::maxpool_fwd);
   m.def("maxpool_bwd", &dtmx::maxpool_bwd);
   m.def("avgpool_fwd", &dtmx::avgpool_fwd, py::arg("x"), py::arg("kernel"),

@@ -219,16 +219,21 @@ struct EpiBF16 {
 // bn_bwd_finalize_slabs + bn_bwd_dx_presummed complete the BN backward.
 // Reference analog: batch_norm.cu:314 BatchNormalizationBackwardKernel,
 // restructured as a GEMM-epilogue fusion.
-template <typename elem_t>
+// MASK: the relu mask comes from the packed bitmask bnb_mask instead of
+// bnb_y (compile-time, so each form issues its loads unconditionally).
+template <typename elem_t, bool MASK = false>
 struct EpiBnBwd {
   using elem = elem_t;
   using V8 = typename E8<elem_t>::v8;
   static constexpr bool kLdsStage = true;
   static constexpr bool kBnBwd = true;
+  static constexpr bool kMask = MASK;
   static constexpr bool kFwdStats = false;
   elem_t* c;             // output: masked gradient g
   const elem_t* acc;     // optional residual-join accumulate (may alias c)
   const elem_t* bnb_y;   // BN(+relu) output (mask source), same [M][N] layout
+  const uint8_t* bnb_mask;  // MASK: packed relu mask [M][N/8] (bit e of byte
+                            // (m, n/8) = !(y[m][n+e] <= 0)); bnb_y is not read
   const elem_t* bnb_x;   // pre-BN conv output (xhat source)
   const float* bnb_mean;    // [N]
   const float* bnb_invstd;  // [N]
@@ -495,19 +500,24 @@ void gemm_tn_kernel(PA pa, PB pb, EPI epi, uint32_t ktiles_total,
         if (rem >= 8) {
           V8 a{};
           if (epi.acc) a = *(const V8*)(epi.acc + off);
-          V8 yv = *(const V8*)(epi.bnb_y + off);
+          // relu mask: one byte per chunk if packed (N % 8 == 0, so
+          // off / 8 = m * (N/8) + n0/8), else the 16-B activation chunk
+          V8 yv{};
+          uint32_t mb = 0;
+          if constexpr (EPI::kMask) mb = epi.bnb_mask[off >> 3];
+          else yv = *(const V8*)(epi.bnb_y + off);
           V8 xv = *(const V8*)(epi.bnb_x + off);
           V8 g;
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             float f = (float)v[e] + (epi.acc ? (float)a[e] : 0.f);
-            if ((float)yv[e] <= 0.f) f = 0.f;
+            if (EPI::kMask ? !((mb >> e) & 1) : (float)yv[e] <= 0.f) f = 0.f;
             g[e] = (elem_t)f;
             db[e] += f;
             dg[e] += f * ((float)xv[e] - mean8[e]) * inv8[e];
           }
           *(V8*)(epi.c + off) = g;
-        } else {
+        } else {  // N % 8 != 0: never with a packed mask (host-checked)
           for (uint32_t e = 0; e < rem; ++e) {
             float f = (float)v[e] + (epi.acc ? (float)epi.acc[off + e] : 0.f);
             if ((float)epi.bnb_y[off + e] <= 0.f) f = 0.f;
@@ -780,19 +790,24 @@ void gemm256f_kernel(PA pa, PB pb, EPI epi, uint32_t ktiles, uint32_t tiles_n) {
         if (rem >= 8) {
           V8 a{};
           if (epi.acc) a = *(const V8*)(epi.acc + off);
-          V8 yv = *(const V8*)(epi.bnb_y + off);
+          // relu mask: one byte per chunk if packed (N % 8 == 0, so
+          // off / 8 = m * (N/8) + n0/8), else the 16-B activation chunk
+          V8 yv{};
+          uint32_t mb = 0;
+          if constexpr (EPI::kMask) mb = epi.bnb_mask[off >> 3];
+          else yv = *(const V8*)(epi.bnb_y + off);
           V8 xv = *(const V8*)(epi.bnb_x + off);
           V8 g;
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             float f = (float)v[e] + (epi.acc ? (float)a[e] : 0.f);
-            if ((float)yv[e] <= 0.f) f = 0.f;
+            if (EPI::kMask ? !((mb >> e) & 1) : (float)yv[e] <= 0.f) f = 0.f;
             g[e] = (elem_t)f;
             db[e] += f;
             dg[e] += f * ((float)xv[e] - mean8[e]) * inv8[e];
           }
           *(V8*)(epi.c + off) = g;
-        } else {
+        } else {  // N % 8 != 0: never with a packed mask (host-checked)
           for (uint32_t e = 0; e < rem; ++e) {
             float f = (float)v[e] + (epi.acc ? (float)epi.acc[off + e] : 0.f);
             if ((float)epi.bnb_y[off + e] <= 0.f) f = 0.f;
@@ -1794,11 +1809,15 @@ at::Tensor conv_dgrad(const at::Tensor& dy, const at::Tensor& w, long stride,
 std::vector<at::Tensor> conv_dgrad_bnfuse(
     const at::Tensor& dy, const at::Tensor& w, long stride, long pad, long H,
     long W_, const c10::optional<at::Tensor>& acc, const at::Tensor& y,
-    const at::Tensor& xin, const at::Tensor& mean, const at::Tensor& invstd) {
+    const at::Tensor& xin, const at::Tensor& mean, const at::Tensor& invstd,
+    const c10::optional<at::Tensor>& mask) {
   DTMX_DISPATCH_16(dy.scalar_type(), "conv_dgrad_bnfuse", {
     CHECK_BF16_CUDA(dy);
     TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast), "dy must be NHWC");
-    TORCH_CHECK(y.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+    // a packed relu mask (bn_fwd_train's 4th output) replaces y, which is
+    // then neither checked nor read
+    const bool have_mask = mask.has_value() && mask->defined();
+    TORCH_CHECK((have_mask || y.is_contiguous(at::MemoryFormat::ChannelsLast)) &&
                     xin.is_contiguous(at::MemoryFormat::ChannelsLast),
                 "bnfuse: y/xin must be NHWC");
     uint32_t N = dy.size(0), Ko = dy.size(1), P = dy.size(2), Q = dy.size(3);
@@ -1806,6 +1825,13 @@ std::vector<at::Tensor> conv_dgrad_bnfuse(
     TORCH_CHECK(!(R == 1 && S == 1 && stride > 1),
                 "conv_dgrad_bnfuse: strided 1x1 (scatter) is not fusable");
     TORCH_CHECK(C % 8 == 0, "conv_dgrad_bnfuse: C must be a multiple of 8");
+    if (have_mask)
+      TORCH_CHECK(mask->scalar_type() == at::kByte &&
+                      mask->device() == dy.device() && mask->dim() == 2 &&
+                      mask->size(0) == (long)N * H * W_ &&
+                      mask->size(1) == (long)C / 8 && mask->is_contiguous(),
+                  "conv_dgrad_bnfuse: mask must be a contiguous uint8 "
+                  "[N*H*W][C/8] tensor on the device of dy");
     at::Tensor dyk = dy.permute({0, 2, 3, 1});
     at::Tensor wtk = w.permute({1, 2, 3, 0});
     if (Ko % 8) {
@@ -1843,34 +1869,38 @@ std::vector<at::Tensor> conv_dgrad_bnfuse(
     // every slab element is written exactly once by its owning block
     auto pdb = at::empty({(long)tiles_m, (long)C}, opt_f);
     auto pdg = at::empty({(long)tiles_m, (long)C}, opt_f);
-    EpiBnBwd<elem_t> epi;
-    epi.c = (elem_t*)dx.data_ptr();
-    epi.acc = have_acc ? (const elem_t*)dx.data_ptr() : nullptr;
-    epi.bnb_y = (const elem_t*)y.data_ptr();
-    epi.bnb_x = (const elem_t*)xin.data_ptr();
-    epi.bnb_mean = mean.data_ptr<float>();
-    epi.bnb_invstd = invstd.data_ptr<float>();
-    epi.bnb_pdb = pdb.data_ptr<float>();
-    epi.bnb_pdg = pdg.data_ptr<float>();
-    epi.M = M;
-    epi.N = C;
-    if (R == 1 && S == 1 && pad == 0) {  // stride==1 guaranteed above
-      DenseP<elem_t> pa{(const elem_t*)dyc.data_ptr(), zero_page<elem_t>(dy),
-                        M, Ko, Ko};
-      DenseP<elem_t> pb{(const elem_t*)wt.data_ptr(), zero_page<elem_t>(dy),
-                        C, Ko, Ko};
-      launch_gemm(pa, pb, epi, M, C, Ko);
-    } else {
-      ConvDgradA<elem_t> pa;
-      pa.dy = (const elem_t*)dyc.data_ptr();
-      pa.zero = zero_page<elem_t>(dy);
-      pa.M = M; pa.Ktot = Ktot; pa.Ko = Ko; pa.H = H; pa.W = W_; pa.P = P;
-      pa.Q = Q; pa.S = S; pa.u = stride; pa.v = stride; pa.ph = pad; pa.pw = pad;
-      pa.dW_.init(W_); pa.dHW.init(H * W_); pa.dKo.init(Ko); pa.dS.init(S);
-      DenseP<elem_t> pb{(const elem_t*)wt.data_ptr(), zero_page<elem_t>(dy),
-                        C, Ktot, Ktot};
-      launch_gemm(pa, pb, epi, M, C, Ktot);
-    }
+    auto run = [&](auto epi) {
+      epi.c = (elem_t*)dx.data_ptr();
+      epi.acc = have_acc ? (const elem_t*)dx.data_ptr() : nullptr;
+      epi.bnb_y = have_mask ? nullptr : (const elem_t*)y.data_ptr();
+      epi.bnb_mask = have_mask ? mask->data_ptr<uint8_t>() : nullptr;
+      epi.bnb_x = (const elem_t*)xin.data_ptr();
+      epi.bnb_mean = mean.data_ptr<float>();
+      epi.bnb_invstd = invstd.data_ptr<float>();
+      epi.bnb_pdb = pdb.data_ptr<float>();
+      epi.bnb_pdg = pdg.data_ptr<float>();
+      epi.M = M;
+      epi.N = C;
+      if (R == 1 && S == 1 && pad == 0) {  // stride==1 guaranteed above
+        DenseP<elem_t> pa{(const elem_t*)dyc.data_ptr(), zero_page<elem_t>(dy),
+                          M, Ko, Ko};
+        DenseP<elem_t> pb{(const elem_t*)wt.data_ptr(), zero_page<elem_t>(dy),
+                          C, Ko, Ko};
+        launch_gemm(pa, pb, epi, M, C, Ko);
+      } else {
+        ConvDgradA<elem_t> pa;
+        pa.dy = (const elem_t*)dyc.data_ptr();
+        pa.zero = zero_page<elem_t>(dy);
+        pa.M = M; pa.Ktot = Ktot; pa.Ko = Ko; pa.H = H; pa.W = W_; pa.P = P;
+        pa.Q = Q; pa.S = S; pa.u = stride; pa.v = stride; pa.ph = pad; pa.pw = pad;
+        pa.dW_.init(W_); pa.dHW.init(H * W_); pa.dKo.init(Ko); pa.dS.init(S);
+        DenseP<elem_t> pb{(const elem_t*)wt.data_ptr(), zero_page<elem_t>(dy),
+                          C, Ktot, Ktot};
+        launch_gemm(pa, pb, epi, M, C, Ktot);
+      }
+    };
+    if (have_mask) run(EpiBnBwd<elem_t, true>{});
+    else run(EpiBnBwd<elem_t, false>{});
     return {dx, pdb, pdg};
   });
   return {};

@@ -26,6 +26,7 @@ import os
 import torch
 import torch.nn.functional as F
 
+from .fusedblock import _relumask_on
 from .hip import require_ext
 
 
@@ -232,11 +233,18 @@ class _BatchNormNHWC(torch.autograd.Function):
                 eps, fuse_relu, residual, pre_psum=None, pre_psumsq=None):
         ext = require_ext()
         if training:
-            y, save_mean, save_invstd = ext.bn_fwd_train(
+            # backward reads y only as the relu mask: keep the packed bitmask
+            # (1/16 of y) instead, so BN does not hold the activation alive
+            # (the stem's 112x112 output feeds a maxpool that saves indices)
+            want_mask = bool(fuse_relu) and _relumask_on()
+            out = ext.bn_fwd_train(
                 x, gamma, beta, running_mean, running_var, momentum, eps,
-                fuse_relu, residual, pre_psum, pre_psumsq
+                fuse_relu, residual, pre_psum, pre_psumsq, want_mask
             )
-            ctx.save_for_backward(x, gamma, save_mean, save_invstd, y)
+            y, save_mean, save_invstd = out[0], out[1], out[2]
+            ctx.save_for_backward(x, gamma, save_mean, save_invstd,
+                                  out[3] if want_mask else y)
+            ctx.has_mask = want_mask
             ctx.fuse_relu = fuse_relu
             ctx.has_residual = residual is not None
         else:
@@ -249,8 +257,12 @@ class _BatchNormNHWC(torch.autograd.Function):
         ext = require_ext()
         x, gamma, save_mean, save_invstd, y = ctx.saved_tensors
         dy = dy.contiguous(memory_format=torch.channels_last)
-        out = ext.bn_bwd(x, dy, gamma, save_mean, save_invstd,
-                         ctx.fuse_relu, y, ctx.has_residual)
+        if ctx.has_mask:  # saved slot holds the mask; y operand is a dummy
+            out = ext.bn_bwd(x, dy, gamma, save_mean, save_invstd,
+                             ctx.fuse_relu, x, ctx.has_residual, mask=y)
+        else:
+            out = ext.bn_bwd(x, dy, gamma, save_mean, save_invstd,
+                             ctx.fuse_relu, y, ctx.has_residual)
         dres = out[3] if ctx.has_residual else None
         return (out[0], out[1], out[2], None, None, None, None, None, None, dres,
                 None, None)

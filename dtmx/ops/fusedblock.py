@@ -48,6 +48,22 @@ def _bnstats_on() -> bool:
     return os.environ.get("DTMX_FUSE_BN_STATS", "1") == "1"
 
 
+def _relumask_on() -> bool:
+    """Packed ReLU bitmask: every fuse_relu BN forward also emits a uint8
+    [rows][C/8] mask (bit e = !(y <= 0)), and the backward kernels that read
+    the 16-bit activation y only for that one bit per element (the EpiBnBwd
+    dgrad epilogue, bn_bwd_stats and the dx kernels) read the mask byte
+    instead. Bit-identical results; DTMX_RELU_MASK=0 restores the y reads."""
+    return os.environ.get("DTMX_RELU_MASK", "1") == "1"
+
+
+def _bn_relu_fwd(ext, c, g, b, bn, mom, eps, res, ps, pss, want_mask):
+    """fuse_relu BN forward -> (y, mean, invstd, mask or None)."""
+    out = ext.bn_fwd_train(c, g, b, bn.running_mean, bn.running_var, mom, eps,
+                           True, res, ps, pss, want_mask)
+    return out[0], out[1], out[2], (out[3] if want_mask else None)
+
+
 def _conv_fs(ext, x, w, stride, pad, want):
     """conv forward, optionally with fused BN-stat slabs."""
     if want:
@@ -83,14 +99,13 @@ class _FusedBottleneck(torch.autograd.Function):
         ext = require_ext()
         mom, eps = bn1.momentum, bn1.eps
         fs = _bnstats_on()
+        mk = _relumask_on()
         c1, ps1, pss1 = _conv_fs(ext, x, w1, 1, 0, fs)
-        y1, m1, i1 = ext.bn_fwd_train(c1, g1, b1, bn1.running_mean,
-                                      bn1.running_var, mom, eps, True, None,
-                                      ps1, pss1)
+        y1, m1, i1, k1 = _bn_relu_fwd(ext, c1, g1, b1, bn1, mom, eps, None,
+                                      ps1, pss1, mk)
         c2, ps2, pss2 = _conv_fs(ext, y1, w2, stride, 1, fs)
-        y2, m2, i2 = ext.bn_fwd_train(c2, g2, b2, bn2.running_mean,
-                                      bn2.running_var, mom, eps, True, None,
-                                      ps2, pss2)
+        y2, m2, i2, k2 = _bn_relu_fwd(ext, c2, g2, b2, bn2, mom, eps, None,
+                                      ps2, pss2, mk)
         c3, ps3, pss3 = _conv_fs(ext, y2, w3, 1, 0, fs)
         if wd is not None:
             cd, psd, pssd = _conv_fs(ext, x, wd, stride, 0, fs)
@@ -100,12 +115,13 @@ class _FusedBottleneck(torch.autograd.Function):
         else:
             cd = sc = x
             md = idn = m1  # placeholders (unused)
-        y3, m3, i3 = ext.bn_fwd_train(c3, g3, b3, bn3.running_mean,
-                                      bn3.running_var, mom, eps, True, sc,
-                                      ps3, pss3)
+        y3, m3, i3, k3 = _bn_relu_fwd(ext, c3, g3, b3, bn3, mom, eps, sc,
+                                      ps3, pss3, mk)
+        # y1/y2 feed the wgrads; y3 is read only as bn3's relu mask, so the
+        # packed mask replaces it
         ctx.save_for_backward(x, w1, g1, w2, g2, w3, g3, wd, gd,
-                              c1, y1, c2, y2, c3, y3, cd, sc,
-                              m1, i1, m2, i2, m3, i3, md, idn)
+                              c1, y1, c2, y2, c3, None if mk else y3, cd, sc,
+                              m1, i1, m2, i2, m3, i3, md, idn, k1, k2, k3)
         ctx.stride = stride
         ctx.has_down = wd is not None
         # cross-block BN-backward fusion handle: the NEXT block's backward
@@ -115,7 +131,7 @@ class _FusedBottleneck(torch.autograd.Function):
         # `handle` dict and the WRAPPER attaches it to the real output.
         ctx.bn3prev = bnprev
         if handle is not None and _bnbwd_on():
-            handle["bnout"] = (c3, m3, i3)
+            handle["bnout"] = (c3, m3, i3, k3)
         return y3
 
     @staticmethod
@@ -123,7 +139,9 @@ class _FusedBottleneck(torch.autograd.Function):
         ext = require_ext()
         (x, w1, g1, w2, g2, w3, g3, wd, gd,
          c1, y1, c2, y2, c3, y3, cd, sc,
-         m1, i1, m2, i2, m3, i3, md, idn) = ctx.saved_tensors
+         m1, i1, m2, i2, m3, i3, md, idn, k1, k2, k3) = ctx.saved_tensors
+        if k3 is not None:
+            y3 = c3  # placeholder operand: never read when a mask is given
         stride = ctx.stride
         fuse = _bnbwd_on() and dy.is_cuda
         dy = _cl(dy)
@@ -142,27 +160,34 @@ class _FusedBottleneck(torch.autograd.Function):
             dres = dy  # already relu-masked at the residual join
         else:
             bnbwd_stats["standalone"] += 1
-            dc3, dg3, db3, dres = ext.bn_bwd(c3, dy, g3, m3, i3, True, y3, True)
+            dc3, dg3, db3, dres = ext.bn_bwd(c3, dy, g3, m3, i3, True, y3, True,
+                                             mask=k3)
         if fuse:
             dy2, pdb2, pdg2 = ext.conv_dgrad_bnfuse(dc3, w3, 1, 0, H2, W2,
-                                                    None, y2, c2, m2, i2)
+                                                    None, y2, c2, m2, i2,
+                                                    mask=k2)
             dc2, dg2, db2 = _bn_bwd_from_masked(ext, c2, dy2, m2, i2, g2,
                                                 pdb2, pdg2)
         else:
             dy2 = ext.conv_dgrad(dc3, w3, 1, 0, H2, W2)
-            dc2, dg2, db2 = ext.bn_bwd(c2, dy2, g2, m2, i2, True, y2, False)
+            dc2, dg2, db2 = ext.bn_bwd(c2, dy2, g2, m2, i2, True, y2, False,
+                                       mask=k2)
         dw3 = ext.conv_wgrad(y2, dc3, 1, 1, 1, 0)
         if fuse:
             dy1, pdb1, pdg1 = ext.conv_dgrad_bnfuse(dc2, w2, stride, 1, H1, W1,
-                                                    None, y1, c1, m1, i1)
+                                                    None, y1, c1, m1, i1,
+                                                    mask=k1)
             dc1, dg1, db1 = _bn_bwd_from_masked(ext, c1, dy1, m1, i1, g1,
                                                 pdb1, pdg1)
         else:
             dy1 = ext.conv_dgrad(dc2, w2, stride, 1, H1, W1)
-            dc1, dg1, db1 = ext.bn_bwd(c1, dy1, g1, m1, i1, True, y1, False)
+            dc1, dg1, db1 = ext.bn_bwd(c1, dy1, g1, m1, i1, True, y1, False,
+                                       mask=k1)
         dw2 = ext.conv_wgrad(y1, dc2, 3, 3, stride, 1)
         dw1 = ext.conv_wgrad(x, dc1, 1, 1, 1, 0)
-        bnp = ctx.bn3prev  # previous block's (c3, mean, invstd) or None
+        # previous block's (c3, mean, invstd, relu mask or None), or None;
+        # with the mask the epilogue no longer reads x as the mask source
+        bnp = ctx.bn3prev
         if ctx.has_down:
             dcd, dgd, dbd = ext.bn_bwd(cd, dres, gd, md, idn, False, sc, False)
             dwd = ext.conv_wgrad(x, dcd, 1, 1, stride, 0)
@@ -170,7 +195,8 @@ class _FusedBottleneck(torch.autograd.Function):
             if fuse and bnp is not None and stride == 1:
                 # last dx producer fuses the PREVIOUS block's bn3 backward
                 dx, pdb, pdg = ext.conv_dgrad_bnfuse(dcd, wd, 1, 0, H, W, dx,
-                                                     x, bnp[0], bnp[1], bnp[2])
+                                                     x, bnp[0], bnp[1], bnp[2],
+                                                     mask=bnp[3])
                 bnbwd_stats["cross_emit"] += 1
                 dx._dtmx_bnslabs = (pdb, pdg)
             else:
@@ -179,7 +205,8 @@ class _FusedBottleneck(torch.autograd.Function):
         else:
             if fuse and bnp is not None:
                 dx, pdb, pdg = ext.conv_dgrad_bnfuse(dc1, w1, 1, 0, H, W, dres,
-                                                     x, bnp[0], bnp[1], bnp[2])
+                                                     x, bnp[0], bnp[1], bnp[2],
+                                                     mask=bnp[3])
                 bnbwd_stats["cross_emit"] += 1
                 dx._dtmx_bnslabs = (pdb, pdg)
             else:
@@ -199,10 +226,10 @@ class _FusedBasicBlock(torch.autograd.Function):
         ext = require_ext()
         mom, eps = bn1.momentum, bn1.eps
         fs = _bnstats_on()
+        mk = _relumask_on()
         c1, ps1, pss1 = _conv_fs(ext, x, w1, stride, 1, fs)
-        y1, m1, i1 = ext.bn_fwd_train(c1, g1, b1, bn1.running_mean,
-                                      bn1.running_var, mom, eps, True, None,
-                                      ps1, pss1)
+        y1, m1, i1, k1 = _bn_relu_fwd(ext, c1, g1, b1, bn1, mom, eps, None,
+                                      ps1, pss1, mk)
         c2, ps2, pss2 = _conv_fs(ext, y1, w2, 1, 1, fs)
         if wd is not None:
             cd, psd, pssd = _conv_fs(ext, x, wd, stride, 0, fs)
@@ -212,23 +239,26 @@ class _FusedBasicBlock(torch.autograd.Function):
         else:
             cd = sc = x
             md = idn = m1
-        y2, m2, i2 = ext.bn_fwd_train(c2, g2, b2, bn2.running_mean,
-                                      bn2.running_var, mom, eps, True, sc,
-                                      ps2, pss2)
-        ctx.save_for_backward(x, w1, g1, w2, g2, wd, gd, c1, y1, c2, y2, cd,
-                              sc, m1, i1, m2, i2, md, idn)
+        y2, m2, i2, k2 = _bn_relu_fwd(ext, c2, g2, b2, bn2, mom, eps, sc,
+                                      ps2, pss2, mk)
+        # y2 is read only as bn2's relu mask: the packed mask replaces it
+        ctx.save_for_backward(x, w1, g1, w2, g2, wd, gd, c1, y1, c2,
+                              None if mk else y2, cd, sc, m1, i1, m2, i2, md,
+                              idn, k1, k2)
         ctx.stride = stride
         ctx.has_down = wd is not None
         ctx.bnprev = bnprev
         if handle is not None and _bnbwd_on():
-            handle["bnout"] = (c2, m2, i2)
+            handle["bnout"] = (c2, m2, i2, k2)
         return y2
 
     @staticmethod
     def backward(ctx, dy):
         ext = require_ext()
         (x, w1, g1, w2, g2, wd, gd, c1, y1, c2, y2, cd, sc,
-         m1, i1, m2, i2, md, idn) = ctx.saved_tensors
+         m1, i1, m2, i2, md, idn, k1, k2) = ctx.saved_tensors
+        if k2 is not None:
+            y2 = c2  # placeholder operand: never read when a mask is given
         stride = ctx.stride
         fuse = _bnbwd_on() and dy.is_cuda
         dy = _cl(dy)
@@ -243,15 +273,18 @@ class _FusedBasicBlock(torch.autograd.Function):
             dres = dy
         else:
             bnbwd_stats["standalone"] += 1
-            dc2, dg2, db2, dres = ext.bn_bwd(c2, dy, g2, m2, i2, True, y2, True)
+            dc2, dg2, db2, dres = ext.bn_bwd(c2, dy, g2, m2, i2, True, y2, True,
+                                             mask=k2)
         if fuse:
             dy1, pdb1, pdg1 = ext.conv_dgrad_bnfuse(dc2, w2, 1, 1, H1, W1,
-                                                    None, y1, c1, m1, i1)
+                                                    None, y1, c1, m1, i1,
+                                                    mask=k1)
             dc1, dg1, db1 = _bn_bwd_from_masked(ext, c1, dy1, m1, i1, g1,
                                                 pdb1, pdg1)
         else:
             dy1 = ext.conv_dgrad(dc2, w2, 1, 1, H1, W1)
-            dc1, dg1, db1 = ext.bn_bwd(c1, dy1, g1, m1, i1, True, y1, False)
+            dc1, dg1, db1 = ext.bn_bwd(c1, dy1, g1, m1, i1, True, y1, False,
+                                       mask=k1)
         dw2 = ext.conv_wgrad(y1, dc2, 3, 3, 1, 1)
         dw1 = ext.conv_wgrad(x, dc1, 3, 3, stride, 1)
         bnp = ctx.bnprev
@@ -261,7 +294,8 @@ class _FusedBasicBlock(torch.autograd.Function):
             dx = ext.conv_dgrad(dc1, w1, stride, 1, H, W)
             if fuse and bnp is not None and stride == 1:
                 dx, pdb, pdg = ext.conv_dgrad_bnfuse(dcd, wd, 1, 0, H, W, dx,
-                                                     x, bnp[0], bnp[1], bnp[2])
+                                                     x, bnp[0], bnp[1], bnp[2],
+                                                     mask=bnp[3])
                 bnbwd_stats["cross_emit"] += 1
                 dx._dtmx_bnslabs = (pdb, pdg)
             else:
@@ -270,7 +304,7 @@ class _FusedBasicBlock(torch.autograd.Function):
             if fuse and bnp is not None:
                 dx, pdb, pdg = ext.conv_dgrad_bnfuse(dc1, w1, stride, 1, H, W,
                                                      dres, x, bnp[0], bnp[1],
-                                                     bnp[2])
+                                                     bnp[2], mask=bnp[3])
                 bnbwd_stats["cross_emit"] += 1
                 dx._dtmx_bnslabs = (pdb, pdg)
             else:

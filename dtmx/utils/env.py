@@ -35,6 +35,8 @@ see profiles/resnet50_mi355x.md for the numbers behind each):
   DTMX_FUSE_BN_STATS    0 = standalone BN fwd stats (no GEMM epilogue fuse)
   DTMX_FUSE_BN_BWD      0 = standalone BN bwd stats (no EpiBnBwd epilogue)
   DTMX_FUSE_BN_CROSS    0 = disable cross-block BN bwd fusion handle
+  DTMX_RELU_MASK        0 = BN backward reads the activation y for the relu
+                        mask (no packed uint8 bitmask from the apply pass)
   DTMX_BN_DX_COEF       0 = direct-form bn_bwd_dx (no coefficient tables)
   DTMX_BN_COL           0 = strided-chunk BN elementwise kernels (no
                         fixed-column register-resident tables)
