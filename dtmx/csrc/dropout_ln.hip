@@ -87,56 +87,66 @@ at::Tensor dropout_bwd(const at::Tensor& dy, const at::Tensor& mask, double p) {
 }
 
 // ---- layernorm ------------------------------------------------------------
-// One 256-thread block per row; fp32 sum/sumsq with wave shuffle + LDS tree.
+// One 256-thread block per row. The row statistics are taken in two passes
+// in fp64: the mean first, then the centred sum of squares. The one-pass
+// fp32 form var = sum(x^2)/D - mean^2 cancels on rows whose mean is large
+// against their spread (rstd off by 0.9 % on fp16 rows 64 + k/16), and an
+// fp32 mean alone leaves (x - mean) wrong where x is close to the mean. The
+// row is cache-resident and LN is off the hot path, so the second pass and
+// the fp64 arithmetic are free; mean and rstd are saved as fp64 for backward.
+
+// sum of v over the block's 256 threads (4 waves), result in every thread
+__device__ __forceinline__ double ln_block_sum(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+  __syncthreads();  // red may still be read from the previous sum
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
 template <typename elem_t>
 __global__ void ln_fwd_kernel(const elem_t* __restrict__ x,
                               const float* __restrict__ gamma,
                               const float* __restrict__ beta,
-                              elem_t* __restrict__ y, float* __restrict__ mean,
-                              float* __restrict__ rstd, uint32_t D, float eps) {
+                              elem_t* __restrict__ y, double* __restrict__ mean,
+                              double* __restrict__ rstd, uint32_t D, double eps) {
   const uint32_t row = blockIdx.x, t = threadIdx.x;
   const elem_t* in = x + (size_t)row * D;
   elem_t* out = y + (size_t)row * D;
-  __shared__ float red[8];
+  __shared__ double red[4];
 
-  float s = 0.f, ss = 0.f;
+  double s = 0.0;
+  for (uint32_t i = t; i < D; i += 256) s += (double)(float)in[i];
+  const double m = ln_block_sum(s, red) / D;
+  double css = 0.0;
   for (uint32_t i = t; i < D; i += 256) {
-    float v = (float)in[i];
-    s += v;
-    ss += v * v;
+    double d = (double)(float)in[i] - m;
+    css += d * d;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s += __shfl_down(s, o);
-    ss += __shfl_down(ss, o);
-  }
-  if ((t & 63) == 0) {
-    red[t >> 6] = s;
-    red[4 + (t >> 6)] = ss;
-  }
-  __syncthreads();
-  s = red[0] + red[1] + red[2] + red[3];
-  ss = red[4] + red[5] + red[6] + red[7];
-  const float m = s / D;
-  const float var = fmaxf(ss / D - m * m, 0.f);
-  const float rs = rsqrtf(var + eps);
+  const double var = ln_block_sum(css, red) / D;
+  const double rs = 1.0 / sqrt(var + eps);
   if (t == 0) {
     mean[row] = m;
     rstd[row] = rs;
   }
-  for (uint32_t i = t; i < D; i += 256)
-    out[i] = (elem_t)(((float)in[i] - m) * rs * gamma[i] + beta[i]);
+  for (uint32_t i = t; i < D; i += 256) {
+    float xh = (float)(((double)(float)in[i] - m) * rs);
+    out[i] = (elem_t)(xh * gamma[i] + beta[i]);
+  }
 }
 
 // dx = rstd * (g - mean_row(g) - xhat * mean_row(g * xhat)),  g = dy * gamma
 // dgamma/dbeta accumulated across rows with fp32 atomics (LN is not on the
-// ResNet hot path; atomics keep it one pass).
+// ResNet hot path; atomics keep it one pass). Each dgamma term dy * xhat is
+// formed in fp64 and rounded once, so the only fp32 errors are that rounding
+// and the adds: within B * 2^-23 * sum|terms|.
 template <typename elem_t>
 __global__ void ln_bwd_kernel(const elem_t* __restrict__ x,
                               const elem_t* __restrict__ dy,
                               const float* __restrict__ gamma,
-                              const float* __restrict__ mean,
-                              const float* __restrict__ rstd,
+                              const double* __restrict__ mean,
+                              const double* __restrict__ rstd,
                               elem_t* __restrict__ dx,
                               float* __restrict__ dgamma,
                               float* __restrict__ dbeta, uint32_t D) {
@@ -144,34 +154,24 @@ __global__ void ln_bwd_kernel(const elem_t* __restrict__ x,
   const elem_t* xr = x + (size_t)row * D;
   const elem_t* dyr = dy + (size_t)row * D;
   elem_t* dxr = dx + (size_t)row * D;
-  const float m = mean[row], rs = rstd[row];
-  __shared__ float red[8];
+  const double m = mean[row], rs = rstd[row];
+  __shared__ double red[4];
 
-  float s1 = 0.f, s2 = 0.f;
+  double s1 = 0.0, s2 = 0.0;
   for (uint32_t i = t; i < D; i += 256) {
-    float xh = ((float)xr[i] - m) * rs;
-    float g = (float)dyr[i] * gamma[i];
+    double xh = ((double)(float)xr[i] - m) * rs;
+    double g = (double)(float)dyr[i] * (double)gamma[i];
     s1 += g;
     s2 += g * xh;
-    atomicAdd(&dgamma[i], (float)dyr[i] * xh);
+    atomicAdd(&dgamma[i], (float)((double)(float)dyr[i] * xh));
     atomicAdd(&dbeta[i], (float)dyr[i]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s1 += __shfl_down(s1, o);
-    s2 += __shfl_down(s2, o);
-  }
-  if ((t & 63) == 0) {
-    red[t >> 6] = s1;
-    red[4 + (t >> 6)] = s2;
-  }
-  __syncthreads();
-  s1 = (red[0] + red[1] + red[2] + red[3]) / D;
-  s2 = (red[4] + red[5] + red[6] + red[7]) / D;
+  s1 = ln_block_sum(s1, red) / D;
+  s2 = ln_block_sum(s2, red) / D;
   for (uint32_t i = t; i < D; i += 256) {
-    float xh = ((float)xr[i] - m) * rs;
-    float g = (float)dyr[i] * gamma[i];
-    dxr[i] = (elem_t)(rs * (g - s1 - xh * s2));
+    double xh = ((double)(float)xr[i] - m) * rs;
+    double g = (double)(float)dyr[i] * (double)gamma[i];
+    dxr[i] = (elem_t)(float)(rs * (g - s1 - xh * s2));
   }
 }
 
@@ -183,13 +183,13 @@ std::vector<at::Tensor> layer_norm_fwd(const at::Tensor& x, const at::Tensor& ga
   auto gf = gamma.to(at::kFloat).contiguous();
   auto bf = beta.to(at::kFloat).contiguous();
   auto y = at::empty_like(xc);
-  auto mean = at::empty({(long)B}, xc.options().dtype(at::kFloat));
-  auto rstd = at::empty({(long)B}, xc.options().dtype(at::kFloat));
+  auto mean = at::empty({(long)B}, xc.options().dtype(at::kDouble));
+  auto rstd = at::empty({(long)B}, xc.options().dtype(at::kDouble));
   DTMX_DISPATCH_16(xc.scalar_type(), "layer_norm_fwd", {
     ln_fwd_kernel<<<B, 256, 0, dl_stream()>>>(
         (const elem_t*)xc.data_ptr(), gf.data_ptr<float>(), bf.data_ptr<float>(),
-        (elem_t*)y.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), D,
-        (float)eps);
+        (elem_t*)y.data_ptr(), mean.data_ptr<double>(), rstd.data_ptr<double>(),
+        D, eps);
   });
   return {y, mean, rstd};
 }
@@ -201,6 +201,12 @@ std::vector<at::Tensor> layer_norm_bwd(const at::Tensor& x, const at::Tensor& dy
   auto xc = x.contiguous();
   auto dyc = dy.contiguous();
   uint32_t B = xc.size(0), D = xc.size(1);
+  TORCH_CHECK(mean.scalar_type() == at::kDouble && rstd.scalar_type() == at::kDouble &&
+                  mean.is_contiguous() && rstd.is_contiguous() &&
+                  mean.numel() == B && rstd.numel() == B,
+              "layer_norm_bwd: mean/rstd must be the fp64 [B] tensors of layer_norm_fwd");
+  TORCH_CHECK(dyc.sizes() == xc.sizes() && dyc.scalar_type() == xc.scalar_type(),
+              "layer_norm_bwd: dy must match x");
   auto gf = gamma.to(at::kFloat).contiguous();
   auto dx = at::empty_like(xc);
   auto dgamma = at::zeros({(long)D}, xc.options().dtype(at::kFloat));
@@ -208,7 +214,7 @@ std::vector<at::Tensor> layer_norm_bwd(const at::Tensor& x, const at::Tensor& dy
   DTMX_DISPATCH_16(xc.scalar_type(), "layer_norm_bwd", {
     ln_bwd_kernel<<<B, 256, 0, dl_stream()>>>(
         (const elem_t*)xc.data_ptr(), (const elem_t*)dyc.data_ptr(),
-        gf.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+        gf.data_ptr<float>(), mean.data_ptr<double>(), rstd.data_ptr<double>(),
         (elem_t*)dx.data_ptr(), dgamma.data_ptr<float>(),
         dbeta.data_ptr<float>(), D);
   });

@@ -348,11 +348,36 @@ at::Tensor global_avgpool_bwd(const at::Tensor& dy, long H, long W) {
   return dx;
 }
 
+// The elementwise kernels walk every operand's storage linearly, so an
+// operand must be one dense block (any dim order) and all operands of a call
+// must agree element for element: same sizes, same strides, same dtype.
+// at::empty_like keeps a dense tensor's strides, so the output agrees too.
+// Strides of size-1 dims address nothing and are not compared.
 #define EW_CHECK(t)                                                        \
+  TORCH_CHECK((t).is_cuda(), #t ": CUDA tensor required");                 \
   TORCH_CHECK((t).scalar_type() == at::kBFloat16 ||                        \
                   (t).scalar_type() == at::kHalf,                          \
-              "16-bit float only");                                        \
-  TORCH_CHECK((t).numel() % 8 == 0, "numel must be a multiple of 8")
+              #t ": 16-bit float only");                                   \
+  TORCH_CHECK((t).numel() > 0 && (t).numel() % 8 == 0,                     \
+              #t ": numel must be a nonzero multiple of 8");               \
+  TORCH_CHECK((t).is_non_overlapping_and_dense(),                          \
+              #t ": must be dense and non-overlapping (strides ",          \
+              (t).strides(), " for sizes ", (t).sizes(), ")");             \
+  TORCH_CHECK((uintptr_t)(t).data_ptr() % 16 == 0,                         \
+              #t ": data pointer must be 16-byte aligned")
+
+static void ew_check_same(const at::Tensor& a, const at::Tensor& b,
+                          const char* an, const char* bn) {
+  TORCH_CHECK(a.scalar_type() == b.scalar_type(), an, " and ", bn,
+              ": same dtype required (", a.scalar_type(), " vs ",
+              b.scalar_type(), ")");
+  TORCH_CHECK(a.sizes() == b.sizes(), an, " and ", bn,
+              ": same sizes required (", a.sizes(), " vs ", b.sizes(), ")");
+  for (int64_t d = 0; d < a.dim(); ++d)
+    TORCH_CHECK(a.size(d) == 1 || a.stride(d) == b.stride(d), an, " and ", bn,
+                ": same strides required (", a.strides(), " vs ", b.strides(),
+                ")");
+}
 
 at::Tensor relu_fwd(const at::Tensor& x) {
   EW_CHECK(x);
@@ -367,6 +392,8 @@ at::Tensor relu_fwd(const at::Tensor& x) {
 
 at::Tensor relu_bwd(const at::Tensor& dy, const at::Tensor& y) {
   EW_CHECK(dy);
+  EW_CHECK(y);
+  ew_check_same(dy, y, "dy", "y");
   auto dx = at::empty_like(dy);
   size_t t8 = dy.numel() / 8;
   DTMX_DISPATCH_16(dy.scalar_type(), "relu_bwd", {
@@ -379,6 +406,8 @@ at::Tensor relu_bwd(const at::Tensor& dy, const at::Tensor& y) {
 
 at::Tensor add_relu_fwd(const at::Tensor& a, const at::Tensor& b) {
   EW_CHECK(a);
+  EW_CHECK(b);
+  ew_check_same(a, b, "a", "b");
   auto y = at::empty_like(a);
   size_t t8 = a.numel() / 8;
   DTMX_DISPATCH_16(a.scalar_type(), "add_relu", {

@@ -40,8 +40,15 @@ __global__ void softmax_ce_fwd_kernel(const elem_t* __restrict__ logits,
   s = red[4] + red[5] + red[6] + red[7];
   const float inv = 1.f / s, logs = __logf(s);
 
-  for (uint32_t i = t; i < V; i += 256)
-    out[i] = (elem_t)(__expf((float)in[i] - m) * inv);
+  // __expf flushes results below 2^-126 (d < -87.34) to zero, which bf16
+  // (fp32's exponent range) can still hold as subnormals: those few
+  // elements take expf. The sum above does not see such terms, and every
+  // other element is computed exactly as before.
+  for (uint32_t i = t; i < V; i += 256) {
+    const float d = (float)in[i] - m;
+    const float e = d < -87.f ? expf(d) : __expf(d);
+    out[i] = (elem_t)(e * inv);
+  }
   if (t == 0) {
     int y = label[row];
     float lp = ((float)in[y] - m) - logs;  // log softmax at the label

@@ -389,12 +389,68 @@ def global_avg_pool(x):
 
 
 # -------------------------------------------------------------- elementwise
+#
+# relu_fwd / relu_bwd / add_relu_fwd walk every operand's storage linearly, so
+# all operands of one call must be dense blocks with the same strides. The
+# helpers below make that true before the kernels are reached; the kernels'
+# host side checks it again and raises instead of computing on mispaired
+# elements.
+
+def _is_dense(t) -> bool:
+    """Non-overlapping and dense: the dims, taken in some order, are
+    contiguous (NCHW, NHWC and any other permutation of a contiguous block;
+    not a slice that leaves gaps)."""
+    expect = 1
+    for stride, size in sorted((st, n) for n, st in zip(t.shape, t.stride())
+                               if n != 1):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def _same_layout(t, like) -> bool:
+    """Same sizes and, for every dim that addresses something, same stride."""
+    return t.shape == like.shape and all(
+        a == b for a, b, n in zip(t.stride(), like.stride(), t.shape) if n != 1)
+
+
+def _dense(t):
+    """`t`, or a dense copy in t's own dim order when t has gaps (a channel
+    slice of an NHWC tensor becomes a smaller NHWC tensor)."""
+    return t if _is_dense(t) else t.clone(memory_format=torch.preserve_format)
+
+
+def _to_layout_of(t, like):
+    """`t` in the memory order of the dense tensor `like` (no copy if it is
+    there already). An upstream gradient arrives in whatever order its
+    producer chose: cat hands out channel slices, reshape NCHW blocks."""
+    if _same_layout(t, like):
+        return t
+    return torch.empty_like(like, dtype=t.dtype).copy_(t)
+
+
+def _ew_in_envelope(*ts) -> bool:
+    """What the vector elementwise kernels take: equal shapes and dtypes and
+    a nonzero multiple of 8 elements. Everything else is torch's."""
+    x = ts[0]
+    return (x.numel() > 0 and x.numel() % 8 == 0
+            and all(t.shape == x.shape and t.dtype == x.dtype
+                    and t.device == x.device for t in ts[1:]))
+
+
+def _aligned(t):
+    """Dense views can start anywhere in their storage; the 16-byte vector
+    loads cannot."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(
+        memory_format=torch.preserve_format)
+
 
 class _ReLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         ext = require_ext()
-        y = ext.relu_fwd(x)
+        y = ext.relu_fwd(_aligned(_dense(x)))
         ctx.save_for_backward(y)
         return y
 
@@ -402,11 +458,11 @@ class _ReLU(torch.autograd.Function):
     def backward(ctx, dy):
         ext = require_ext()
         (y,) = ctx.saved_tensors
-        return ext.relu_bwd(dy.contiguous(memory_format=_mf(dy)), y)
+        return ext.relu_bwd(_aligned(_to_layout_of(dy, y)), y)
 
 
 def relu(x):
-    if _use_hip(x, op="relu"):
+    if _use_hip(x, op="relu") and _ew_in_envelope(x):
         return _ReLU.apply(x)
     return F.relu(x)
 
@@ -415,7 +471,8 @@ class _AddRelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
         ext = require_ext()
-        y = ext.add_relu_fwd(a, b)
+        a = _aligned(_dense(a))
+        y = ext.add_relu_fwd(a, _aligned(_to_layout_of(b, a)))
         ctx.save_for_backward(y)
         return y
 
@@ -423,23 +480,15 @@ class _AddRelu(torch.autograd.Function):
     def backward(ctx, dy):
         ext = require_ext()
         (y,) = ctx.saved_tensors
-        g = ext.relu_bwd(dy.contiguous(memory_format=_mf(dy)), y)
+        g = ext.relu_bwd(_aligned(_to_layout_of(dy, y)), y)
         return g, g
 
 
 def add_relu(a, b):
     """Fused residual add + ReLU (resnet hot path: one HBM round trip)."""
-    if _use_hip(a, op="relu"):
+    if _use_hip(a, b, op="relu") and _ew_in_envelope(a, b):
         return _AddRelu.apply(a, b)
     return F.relu(a + b)
-
-
-def _mf(t):
-    return (
-        torch.channels_last
-        if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
-        else torch.contiguous_format
-    )
 
 
 class _LRN(torch.autograd.Function):
@@ -560,7 +609,8 @@ def dropout(x, p: float, training: bool, seed: int | None = None):
 
 class _LayerNorm(torch.autograd.Function):
     """Row LayerNorm (reference src/operator/nn/layer_norm.cu): one block per
-    row, fp32 accumulation; dgamma/dbeta via fp32 atomics."""
+    row, two-pass fp64 row statistics (saved as fp64 mean/rstd); dgamma/dbeta
+    via fp32 atomics."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
