@@ -81,6 +81,23 @@ void sgd_mom_mp_dev(at::Tensor, const at::Tensor&, at::Tensor, at::Tensor,
                     const at::Tensor&);
 void sgd_mom_f32(at::Tensor, const at::Tensor&, at::Tensor, double, double,
                  double, double, double);
+// optimizer.hip
+int64_t opt_chunk();
+void seg_sqnorm(const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                at::Tensor, at::Tensor, at::Tensor, double, double, double,
+                double, double, const c10::optional<at::Tensor>&, int64_t);
+void lbsgd_mom_mp(at::Tensor, const at::Tensor&, at::Tensor, at::Tensor,
+                  const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                  const at::Tensor&, const at::Tensor&, double, double, double,
+                  double);
+void lbsgd_mom_mp_dev(at::Tensor, const at::Tensor&, at::Tensor, at::Tensor,
+                      const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                      const at::Tensor&, const at::Tensor&, const at::Tensor&);
+void nag_mom_mp(at::Tensor, const at::Tensor&, at::Tensor, at::Tensor, double,
+                double, double, double, double);
+void nag_mom_mp_dev(at::Tensor, const at::Tensor&, at::Tensor, at::Tensor,
+                    const at::Tensor&);
 // dropout_ln.hip
 std::vector<at::Tensor> dropout_fwd(const at::Tensor&, double, int64_t);
 at::Tensor dropout_bwd(const at::Tensor&, const at::Tensor&, double);
@@ -171,6 +188,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sgd_mom_mp", &dtmx::sgd_mom_mp);
   m.def("sgd_mom_mp_dev", &dtmx::sgd_mom_mp_dev);
   m.def("sgd_mom_f32", &dtmx::sgd_mom_f32);
+  // Segment ("per-parameter") view of a flat bucket: chunk tables are device
+  // int32, seg_off is their host copy (CPU int32, nseg+1 entries). seg_sqnorm
+  // fills part [nchunks][2] f32, sq [nseg][2] f64 = {sum master^2, sum g^2}
+  // and seg_lr [nseg] f32; stages 1 / 2 / 3 = partials / final / both. With
+  // `hyper` (device f32 {lr, momentum, wd, rescale, clip, eta}) the scalar
+  // arguments are ignored.
+  m.def("opt_chunk", &dtmx::opt_chunk);
+  m.def("seg_sqnorm", &dtmx::seg_sqnorm, py::arg("grad"), py::arg("master"),
+        py::arg("chunk_start"), py::arg("chunk_len"), py::arg("seg_chunk_off"),
+        py::arg("seg_off"), py::arg("part"), py::arg("sq"), py::arg("seg_lr"),
+        py::arg("lr"), py::arg("wd"), py::arg("rescale"), py::arg("clip"),
+        py::arg("eta"), py::arg("hyper") = py::none(), py::arg("stages") = 3);
+  m.def("lbsgd_mom_mp", &dtmx::lbsgd_mom_mp, py::arg("w"), py::arg("grad"),
+        py::arg("master"), py::arg("mom"), py::arg("chunk_seg"),
+        py::arg("chunk_start"), py::arg("chunk_len"), py::arg("seg_lr"),
+        py::arg("seg_off"), py::arg("momentum"), py::arg("wd"),
+        py::arg("rescale"), py::arg("clip"));
+  m.def("lbsgd_mom_mp_dev", &dtmx::lbsgd_mom_mp_dev, py::arg("w"),
+        py::arg("grad"), py::arg("master"), py::arg("mom"), py::arg("chunk_seg"),
+        py::arg("chunk_start"), py::arg("chunk_len"), py::arg("seg_lr"),
+        py::arg("seg_off"), py::arg("hyper"));
+  m.def("nag_mom_mp", &dtmx::nag_mom_mp);
+  m.def("nag_mom_mp_dev", &dtmx::nag_mom_mp_dev);
   m.def("dropout_fwd", &dtmx::dropout_fwd);
   m.def("dropout_bwd", &dtmx::dropout_bwd);
   m.def("layer_norm_fwd", &dtmx::layer_norm_fwd);

@@ -42,6 +42,7 @@ from ..kvstore import KVStore, DistKVStore, LocalKVStore
 from ..lr_scheduler import WarmupScheduler
 from ..optimizer import Optimizer, Updater, create as opt_create, get_updater
 from ..parallel.bucketer import GradBucketer
+from ..utils.env import get_env_bool
 
 
 def _as_list(x):
@@ -80,7 +81,8 @@ class Module:
         self._optimizer: Optional[Optimizer] = None
         self._update_on_kvstore = True
         self._bucketer: Optional[GradBucketer] = None
-        self._use_fused_sgd = False
+        self._use_fused_sgd = False   # the flat (fused optimizer) path is on
+        self._fused_kind = None       # "sgd" | "nag" | "lbsgd" when it is
         self._batch_size = 0
         # hipGraph step capture (HIP graphs in place of the reference's
         # op-segment bulking, graph_executor.cc:1318)
@@ -252,21 +254,34 @@ class Module:
                 for name, b in auxs.items():
                     kv.init(name, b.data, exclude_update=True)
         # gradient bucketing (+ comm overlap when distributed). On GPU with
-        # plain SGD+bf16, parameters are flattened so the whole optimizer
-        # step is one fused HIP kernel per bucket.
+        # SGD, NAG or LBSGD (exact types) and a 16-bit dtype, parameters are
+        # flattened so the whole optimizer step is one fused HIP kernel per
+        # bucket (LBSGD: plus two small norm launches). _use_fused_sgd is the
+        # "flat path is on" flag, _fused_kind says which step runs on it.
+        from ..optimizer.optimizer import LBSGD as _LBSGD
+        from ..optimizer.optimizer import NAG as _NAG
         from ..optimizer.optimizer import SGD as _SGD
 
         on_gpu = self.device.type == "cuda"
+        kind = {_SGD: "sgd", _NAG: "nag", _LBSGD: "lbsgd"}.get(type(optimizer))
         self._use_fused_sgd = (
             on_gpu
-            and type(optimizer) is _SGD
+            and kind is not None
             and self._dtype in (torch.bfloat16, torch.float16)
             and not self.fixed_param_names
         )
+        if self._use_fused_sgd and kind != "sgd":
+            # the flat kernels take one lr and one wd per bucket; DTMX_FUSED_OPT
+            # is read here, when the optimizer is initialised
+            self._use_fused_sgd = (
+                not optimizer.lr_mult and not optimizer.wd_mult
+                and get_env_bool("DTMX_FUSED_OPT", True)
+            )
         if self._use_fused_sgd:
             from ..ops.hip import has_ext
 
             self._use_fused_sgd = has_ext()
+        self._fused_kind = kind if self._use_fused_sgd else None
         if not self._use_fused_sgd:
             # eagerly create optimizer state so elastic state broadcasts are
             # well-defined on every rank (momenta exist before any update)
@@ -363,13 +378,26 @@ class Module:
                 opt = self._optimizer
                 opt.num_update += 1
                 lr = opt.lr_scheduler(opt.num_update) if opt.lr_scheduler else opt.lr
+                if self._fused_kind == "lbsgd":
+                    lr = opt.warmup_lr(lr, opt.num_update)
                 hyper = None
                 if self._capture_mode:
                     hyper = self._update_hyper(lr)
-                self._bucketer.fused_sgd_step(
-                    lr, getattr(opt, "momentum", 0.0), opt.wd, opt.rescale_grad,
-                    opt.clip_gradient or 0.0, hyper=hyper,
-                )
+                if self._fused_kind == "sgd":
+                    self._bucketer.fused_sgd_step(
+                        lr, getattr(opt, "momentum", 0.0), opt.wd, opt.rescale_grad,
+                        opt.clip_gradient or 0.0, hyper=hyper,
+                    )
+                elif self._fused_kind == "nag":
+                    self._bucketer.fused_nag_step(
+                        lr, opt.momentum, opt.wd, opt.rescale_grad,
+                        opt.clip_gradient or 0.0, hyper=hyper,
+                    )
+                else:
+                    self._bucketer.fused_lbsgd_step(
+                        lr, opt.momentum, opt.wd, opt.rescale_grad,
+                        opt.clip_gradient or 0.0, opt.eta, hyper=hyper,
+                    )
             else:
                 grads = (
                     self._bucketer.reduced_views()
@@ -396,15 +424,19 @@ class Module:
 
     # -------------------------------------------------- hipGraph step replay
     def _update_hyper(self, lr: float) -> torch.Tensor:
+        """Device {lr, momentum, wd, rescale, clip, eta} for the *_dev kernels;
+        `lr` is the step's final lr (LBSGD: warmup ramp applied). eta is read
+        by the LBSGD norm kernel only."""
         opt = self._optimizer
         if self._hyper_dev is None:
-            self._hyper_dev = torch.zeros(5, dtype=torch.float32, device=self.device)
-            self._hyper_host = torch.zeros(5, dtype=torch.float32, pin_memory=True)
+            self._hyper_dev = torch.zeros(6, dtype=torch.float32, device=self.device)
+            self._hyper_host = torch.zeros(6, dtype=torch.float32, pin_memory=True)
         self._hyper_host[0] = lr
         self._hyper_host[1] = getattr(opt, "momentum", 0.0)
         self._hyper_host[2] = opt.wd
         self._hyper_host[3] = opt.rescale_grad
         self._hyper_host[4] = opt.clip_gradient or 0.0
+        self._hyper_host[5] = getattr(opt, "eta", 0.0)
         self._hyper_dev.copy_(self._hyper_host, non_blocking=True)
         return self._hyper_dev
 
@@ -463,11 +495,12 @@ class Module:
                     dst.copy_(self._to_device(src, False), non_blocking=True)
         # increment num_update BEFORE deriving lr, matching the eager
         # update() path — otherwise replayed steps run one lr-update stale.
-        self._optimizer.num_update += 1
-        self._update_hyper(
-            self._optimizer.lr_scheduler(self._optimizer.num_update)
-            if self._optimizer.lr_scheduler else self._optimizer.lr
-        )
+        opt = self._optimizer
+        opt.num_update += 1
+        lr = opt.lr_scheduler(opt.num_update) if opt.lr_scheduler else opt.lr
+        if self._fused_kind == "lbsgd":
+            lr = opt.warmup_lr(lr, opt.num_update)
+        self._update_hyper(lr)
         self._graph.replay()
 
     def store_aux_params(self):
@@ -639,6 +672,7 @@ class Module:
         if self._use_fused_sgd and self._bucketer is not None:
             payload = {
                 "fused": True,
+                "kind": self._fused_kind,
                 "master": [t.cpu() for t in self._bucketer.flat_master],
                 "mom": [t.cpu() for t in self._bucketer.flat_mom],
                 "num_update": self._optimizer.num_update,
@@ -657,6 +691,11 @@ class Module:
             payload = pickle.load(f)
         if isinstance(payload, dict) and payload.get("fused"):
             assert self._use_fused_sgd and self._bucketer is not None
+            kind = payload.get("kind", "sgd")  # payloads without the key are SGD's
+            if kind != self._fused_kind:
+                raise ValueError(
+                    "optimizer states in %s were saved by the fused '%s' step; "
+                    "this module runs the fused '%s' step" % (fname, kind, self._fused_kind))
             with torch.no_grad():
                 for dst, src in zip(self._bucketer.flat_master, payload["master"]):
                     dst.copy_(src.to(dst.device))

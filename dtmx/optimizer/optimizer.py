@@ -16,9 +16,9 @@ Semantics preserved from the reference:
 - num_update bookkeeping per index drives the lr scheduler
   (reference optimizer.py:85-113).
 
-On MI355X the fused multi-tensor SGD step runs in the HIP extension
-(dtmx/csrc/optimizer.hip); this module is the per-tensor semantic reference
-and the CPU path.
+On MI355X the fused multi-tensor SGD, NAG and LBSGD steps run in the HIP
+extension (dtmx/csrc/softmax_opt.hip sgd_mom_mp, dtmx/csrc/optimizer.hip);
+this module is the per-tensor semantic reference and the CPU path.
 """
 from __future__ import annotations
 
@@ -211,17 +211,22 @@ class LBSGD(SGD):
         self.batch_scale = batch_scale
         self.eta = eta
 
-    def update(self, index, weight, grad, state):
-        self._update_count(index)
-        lr = self._get_lr(index)
-        wd = self._get_wd(index)
-        # warmup ramp
-        t = self.num_update
+    def warmup_lr(self, lr: float, t: int) -> float:
+        """`lr` under the warmup ramp at update count `t`; shared with the
+        fused flat-bucket step (Module.update), which folds the ramp into the
+        lr it hands to the kernels."""
         if t < self.warmup_updates:
             if self.warmup_strategy == "linear":
                 lr = lr * (t + 1) / self.warmup_updates
             elif self.warmup_strategy == "sqrt":
                 lr = lr * math.sqrt((t + 1) / self.warmup_updates)
+        return lr
+
+    def update(self, index, weight, grad, state):
+        self._update_count(index)
+        lr = self._get_lr(index)
+        wd = self._get_wd(index)
+        lr = self.warmup_lr(lr, self.num_update)
         g = self._preprocess(index, grad).to(torch.float32)
         with torch.no_grad():
             w32 = weight if weight.dtype == torch.float32 else weight.float()

@@ -24,13 +24,66 @@ import torch
 import torch.distributed as dist
 
 
+# Elements per chunk of the segment tables; equals OPT_CHUNK of
+# dtmx/csrc/optimizer.hip (checked against ext.opt_chunk() when tables are
+# uploaded).
+OPT_CHUNK = 4096
+
+
+def build_segment_tables(sizes: Sequence[int], chunk: int = OPT_CHUNK) -> Dict[str, List[int]]:
+    """Per-parameter ("segment") view of a flat bucket, as plain int lists.
+
+    Segment s is the element range [seg_off[s], seg_off[s+1]) of the flat. It
+    is cut into chunks of at most `chunk` consecutive elements, counted from
+    the segment's start, so no chunk straddles two segments and a parameter's
+    chunking depends on its own size only. chunk_start is an index into the
+    flat; seg_chunk_off[s] is the first chunk of segment s (nseg+1 entries).
+    A zero-size segment has no chunk."""
+    assert chunk > 0
+    seg_off, chunk_seg, chunk_start, chunk_len, seg_chunk_off = [0], [], [], [], [0]
+    for s, n in enumerate(sizes):
+        n = int(n)
+        assert n >= 0
+        base = seg_off[-1]
+        for o in range(0, n, chunk):
+            chunk_seg.append(s)
+            chunk_start.append(base + o)
+            chunk_len.append(min(chunk, n - o))
+        seg_off.append(base + n)
+        seg_chunk_off.append(len(chunk_seg))
+    assert seg_off[-1] < 2 ** 31, "a flat bucket must hold fewer than 2^31 elements"
+    return {"seg_off": seg_off, "chunk_seg": chunk_seg, "chunk_start": chunk_start,
+            "chunk_len": chunk_len, "seg_chunk_off": seg_chunk_off}
+
+
+class SegmentTables:
+    """Device copy of build_segment_tables() for one bucket plus the persistent
+    norm workspaces: part [nchunks][2] f32 per-chunk {sum master^2, sum g^2},
+    sq [nseg][2] f64 per-segment sums, seg_lr [nseg] f32. Derived data, not
+    optimizer state."""
+
+    def __init__(self, sizes: Sequence[int], device, chunk: int = OPT_CHUNK):
+        t = build_segment_tables(sizes, chunk)
+        i32 = lambda v, dev: torch.tensor(v, dtype=torch.int32, device=dev)
+        self.seg_off = i32(t["seg_off"], "cpu")       # host copy (validation)
+        self.chunk_seg = i32(t["chunk_seg"], device)
+        self.chunk_start = i32(t["chunk_start"], device)
+        self.chunk_len = i32(t["chunk_len"], device)
+        self.seg_chunk_off = i32(t["seg_chunk_off"], device)
+        self.nseg, self.nchunks = len(sizes), len(t["chunk_seg"])
+        self.part = torch.empty(self.nchunks, 2, dtype=torch.float32, device=device)
+        self.sq = torch.zeros(self.nseg, 2, dtype=torch.float64, device=device)
+        self.seg_lr = torch.zeros(self.nseg, dtype=torch.float32, device=device)
+
+
 class GradBucketer:
     """With `flatten_params=True` the parameters themselves are also moved
     into per-bucket flat bf16 buffers (p.data becomes a [strided] view), plus
     fp32 master and momentum flats — so the whole optimizer step is ONE fused
-    HIP kernel per bucket (dtmx/csrc/softmax_opt.hip sgd_mom_mp) instead of
-    2-4 torch ops per tensor (reference optimizer_op-inl.h MP_SGDMom redesign
-    as a multi-tensor kernel)."""
+    HIP kernel per bucket (dtmx/csrc/softmax_opt.hip sgd_mom_mp; for NAG and
+    LBSGD dtmx/csrc/optimizer.hip, LBSGD with two small norm launches in
+    front) instead of 2-4 torch ops per tensor (reference optimizer_op-inl.h
+    MP_SGDMom redesign as a multi-tensor kernel)."""
 
     def __init__(self, params: Sequence[torch.nn.Parameter],
                  bucket_mb: Optional[float] = None, average: bool = False,
@@ -48,6 +101,7 @@ class GradBucketer:
         self.flat_w: List[torch.Tensor] = []
         self.flat_master: List[torch.Tensor] = []
         self.flat_mom: List[torch.Tensor] = []
+        self._seg_tables: Optional[List[SegmentTables]] = None
         bucket_mb = bucket_mb or float(os.environ.get("DTMX_BUCKET_MB", "50"))
         bucket_bytes = int(bucket_mb * 1024 * 1024)
 
@@ -143,6 +197,67 @@ class GradBucketer:
                                    self.flat_master[bi], self.flat_mom[bi], hyper)
             else:
                 ext.sgd_mom_mp(self.flat_w[bi], grads[bi], self.flat_master[bi],
+                               self.flat_mom[bi], lr, momentum, wd, rescale, clip)
+
+    def segment_tables(self) -> List[SegmentTables]:
+        """Per-bucket segment/chunk tables and norm workspaces, built on first
+        use (only the LBSGD step needs them)."""
+        if self._seg_tables is None:
+            assert self.flatten_params, "segment tables need flatten_params=True"
+            from ..ops.hip import require_ext
+
+            assert require_ext().opt_chunk() == OPT_CHUNK
+            self._seg_tables = [
+                SegmentTables([p.numel() for p in bucket], self.flat_w[bi].device)
+                for bi, bucket in enumerate(self.buckets)
+            ]
+        return self._seg_tables
+
+    def fused_lbsgd_step(self, lr: float, momentum: float, wd: float,
+                         rescale: float, clip: float = 0.0, eta: float = 0.001,
+                         hyper: Optional[torch.Tensor] = None):
+        """LBSGD on the flats: per bucket, two small launches reduce every
+        parameter's |master|^2 and |g|^2 and write its trust-ratio learning
+        rate (tables.seg_lr), then one launch applies the sgd_mom_mp body with
+        that rate. `lr` already carries the warmup ramp. No host sync.
+        hyper: optional device float32[6] {lr,mom,wd,rescale,clip,eta}, as in
+        fused_sgd_step."""
+        from ..ops.hip import require_ext
+
+        ext = require_ext()
+        grads = self.reduced_flats() if self.async_mode else self.flat
+        tabs = self.segment_tables()
+        for bi in range(len(self.flat)):
+            t = tabs[bi]
+            ext.seg_sqnorm(grads[bi], self.flat_master[bi], t.chunk_start,
+                           t.chunk_len, t.seg_chunk_off, t.seg_off, t.part, t.sq,
+                           t.seg_lr, lr, wd, rescale, clip, eta, hyper)
+            if hyper is not None:
+                ext.lbsgd_mom_mp_dev(self.flat_w[bi], grads[bi],
+                                     self.flat_master[bi], self.flat_mom[bi],
+                                     t.chunk_seg, t.chunk_start, t.chunk_len,
+                                     t.seg_lr, t.seg_off, hyper)
+            else:
+                ext.lbsgd_mom_mp(self.flat_w[bi], grads[bi], self.flat_master[bi],
+                                 self.flat_mom[bi], t.chunk_seg, t.chunk_start,
+                                 t.chunk_len, t.seg_lr, t.seg_off, momentum, wd,
+                                 rescale, clip)
+
+    def fused_nag_step(self, lr: float, momentum: float, wd: float,
+                       rescale: float, clip: float = 0.0,
+                       hyper: Optional[torch.Tensor] = None):
+        """Nesterov momentum on the flats, one launch per bucket. hyper as in
+        fused_sgd_step (a sixth entry is ignored)."""
+        from ..ops.hip import require_ext
+
+        ext = require_ext()
+        grads = self.reduced_flats() if self.async_mode else self.flat
+        for bi in range(len(self.flat)):
+            if hyper is not None:
+                ext.nag_mom_mp_dev(self.flat_w[bi], grads[bi],
+                                   self.flat_master[bi], self.flat_mom[bi], hyper)
+            else:
+                ext.nag_mom_mp(self.flat_w[bi], grads[bi], self.flat_master[bi],
                                self.flat_mom[bi], lr, momentum, wd, rescale, clip)
 
     def state_tensors(self) -> List[torch.Tensor]:

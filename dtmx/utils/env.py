@@ -32,6 +32,9 @@ Engine / debugging:
 Kernel dispatch (all measured defaults; the off-switches exist for A/B —
 see profiles/resnet50_mi355x.md for the numbers behind each):
   DTMX_FUSED_BLOCK      0 = disable fused ResNet block backward
+  DTMX_FUSED_OPT        0 = NAG and LBSGD take the per-tensor optimizer loop,
+                        not the fused flat-bucket step (read when
+                        Module.init_optimizer runs; plain SGD is not affected)
   DTMX_FUSE_BN_STATS    0 = standalone BN fwd stats (no GEMM epilogue fuse)
   DTMX_FUSE_BN_BWD      0 = standalone BN bwd stats (no EpiBnBwd epilogue)
   DTMX_FUSE_BN_CROSS    0 = disable cross-block BN bwd fusion handle
