@@ -10,6 +10,11 @@ at::Tensor conv_fwd(const at::Tensor&, const at::Tensor&, long, long);
 at::Tensor conv_dgrad(const at::Tensor&, const at::Tensor&, long, long, long, long,
                       const c10::optional<at::Tensor>&);
 at::Tensor conv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, long);
+at::Tensor conv_wgrad_nt256(const at::Tensor&, const at::Tensor&, long, long, long,
+                            long, long, bool);
+std::tuple<bool, long, bool> wgrad_nt256_plan(long, long, long);
+at::Tensor conv_wgrad_acc32(const at::Tensor&, const at::Tensor&, long, long, long,
+                            long, bool, long, bool);
 std::vector<at::Tensor> conv_dgrad_bnfuse(const at::Tensor&, const at::Tensor&,
                                           long, long, long, long,
                                           const c10::optional<at::Tensor>&,
@@ -131,6 +136,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stride"), py::arg("pad"), py::arg("H"), py::arg("W"),
         py::arg("acc") = c10::nullopt);
   m.def("conv_wgrad", &dtmx::conv_wgrad);
+  // test/bench entry: always the 256² contraction-major kernel
+  m.def("conv_wgrad_nt256", &dtmx::conv_wgrad_nt256, py::arg("x"),
+        py::arg("dy"), py::arg("R"), py::arg("S"), py::arg("stride"),
+        py::arg("pad"), py::arg("splitk"), py::arg("group"));
+  // test entry: fp32 split-K sums before the 16-bit rounding
+  m.def("conv_wgrad_acc32", &dtmx::conv_wgrad_acc32, py::arg("x"),
+        py::arg("dy"), py::arg("R"), py::arg("S"), py::arg("stride"),
+        py::arg("pad"), py::arg("nt256"), py::arg("splitk"), py::arg("group"));
+  // (use, splitk, group) the routing picks for a (Ko, RSC, NPQ) wgrad
+  m.def("wgrad_nt256_plan", &dtmx::wgrad_nt256_plan, py::arg("Ko"),
+        py::arg("RSC"), py::arg("NPQ"));
   m.def("dwconv_fwd", &dtmx::dwconv_fwd, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("pad"));
   m.def("dwconv_dgrad", &dtmx::dwconv_dgrad, py::arg("dy"), py::arg("w"),
