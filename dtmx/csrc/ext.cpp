@@ -34,6 +34,10 @@ at::Tensor gconv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, b
 // avgpool.hip
 at::Tensor avgpool_fwd(const at::Tensor&, long, long, long, bool);
 at::Tensor avgpool_bwd(const at::Tensor&, long, long, long, long, long, bool);
+// augment.hip
+at::Tensor augment_batch(const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                         const at::Tensor&, const at::Tensor&, long, long,
+                         at::ScalarType, const at::Tensor&, const at::Tensor&);
 // batchnorm.hip
 std::vector<at::Tensor> bn_fwd_train(const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, at::Tensor, at::Tensor,
@@ -194,6 +198,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("avgpool_bwd", &dtmx::avgpool_bwd, py::arg("dy"), py::arg("H"),
         py::arg("W"), py::arg("kernel"), py::arg("stride"), py::arg("pad"),
         py::arg("count_include_pad"));
+  // Decoded uint8 records -> normalised (B,3,TH,TW) channels_last batch; the
+  // plan row layout is documented in augment.hip. geom / par are device
+  // tensors, geom_host / par_host their CPU copies (validated on the host);
+  // mean / std are 3-element CPU float32 tensors.
+  m.def("augment_batch", &dtmx::augment_batch, py::arg("src"), py::arg("geom"),
+        py::arg("par"), py::arg("mean"), py::arg("std"), py::arg("TH"),
+        py::arg("TW"), py::arg("out_dtype"), py::arg("geom_host"),
+        py::arg("par_host"));
   m.def("global_avgpool_fwd", &dtmx::global_avgpool_fwd);
   m.def("global_avgpool_bwd", &dtmx::global_avgpool_bwd);
   m.def("relu_fwd", &dtmx::relu_fwd);

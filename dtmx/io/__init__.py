@@ -390,7 +390,35 @@ class ImageRecordIter(DataIter):
     threaded record parsing + JPEG decode (libjpeg) + resize/random-crop/
     mirror augmentation + batch assembly + bounded prefetch queue, sharded
     by (part_index, num_parts). Records carry JPEG payloads or raw uint8
-    HWC of the target shape (tools/im2rec.py packs both)."""
+    HWC of the target shape (tools/im2rec.py packs both).
+
+    Two paths. The constructor arguments up to `std_b` alone keep the first
+    one: workers resize / crop / mirror on the CPU and hand out fp32 batches.
+    Any of the augmentation flags after them, or `device`, selects the staged
+    path: workers only decode and draw each record's plan, and one
+    `dtmx.io.augment.augment_batch` pass (a HIP kernel for `device="cuda"`,
+    torch on the CPU) resamples once, applies colour jitter, PCA lighting and
+    mean/std, and writes the channels_last batch in `dtype` (bf16 by default
+    on a GPU, fp32 on the CPU). With `prefetch_to_device` the copy and kernel
+    of batch k+1 run on a private stream while batch k trains.
+
+    On the staged path a raw record may have any size: its header's `id2`
+    field names it as `(H << 32) | W`, and counts only when the payload is
+    exactly H*W*3 bytes (`tools/im2rec.py --raw-size` writes such records);
+    every other raw record has the target shape, as on the first path.
+
+    Reference flags that are not implemented (`max_rotate_angle`, `rotate`,
+    `max_shear_ratio`, `min/max_random_scale`, `min/max_img_size`,
+    `random_h/s/l`, `inter_method != 1`) raise ValueError. Any other unknown
+    keyword is ignored with one warning per name and process."""
+
+    # reference flags this iterator does not implement, with the default a
+    # caller may still pass
+    _UNSUPPORTED = {"max_rotate_angle": 0, "rotate": -1, "max_shear_ratio": 0,
+                    "min_random_scale": 1, "max_random_scale": 1,
+                    "min_img_size": 0, "max_img_size": 1e10, "random_h": 0,
+                    "random_s": 0, "random_l": 0, "inter_method": 1}
+    _warned_kwargs: set = set()
 
     def __init__(self, path_imgrec: str, data_shape, batch_size: int,
                  shuffle: bool = False, part_index: int = 0, num_parts: int = 1,
@@ -399,15 +427,71 @@ class ImageRecordIter(DataIter):
                  rand_crop: bool = False, rand_mirror: bool = False,
                  resize: int = 0, mean_r: float = 0.0, mean_g: float = 0.0,
                  mean_b: float = 0.0, std_r: float = 1.0, std_g: float = 1.0,
-                 std_b: float = 1.0, **kwargs):
+                 std_b: float = 1.0, random_resized_crop: bool = False,
+                 min_random_area: float = 1.0, max_random_area: float = 1.0,
+                 min_aspect_ratio: Optional[float] = None,
+                 max_aspect_ratio: float = 0.0, min_crop_size: int = -1,
+                 max_crop_size: int = -1, pad: int = 0, fill_value: int = 255,
+                 brightness: float = 0.0, contrast: float = 0.0,
+                 saturation: float = 0.0, pca_noise: float = 0.0,
+                 device=None, dtype: Optional[torch.dtype] = None,
+                 prefetch_to_device: bool = True, **kwargs):
         super().__init__(batch_size)
         from dtmx.ops.hip import require_ext
 
         ext = require_ext()
+        for name, default in self._UNSUPPORTED.items():
+            if name in kwargs and kwargs.pop(name) != default:
+                raise ValueError(f"ImageRecordIter: {name} is not implemented")
+        unknown = sorted(set(kwargs) - self._warned_kwargs)
+        if unknown:
+            import logging
+
+            type(self)._warned_kwargs.update(unknown)
+            logging.warning("ImageRecordIter: ignoring unknown arguments %s",
+                            ", ".join(unknown))
+        if random_resized_crop:
+            for name, on in (("rand_crop", rand_crop),
+                             ("min_crop_size", min_crop_size != -1),
+                             ("max_crop_size", max_crop_size != -1)):
+                if on:
+                    raise ValueError("ImageRecordIter: random_resized_crop "
+                                     f"conflicts with {name}")
         self._reader = ext.RecordIOReader(path_imgrec)
         # data_shape is CHW (reference convention); records store HWC raw
         c, h, w = data_shape
         self._chw = (c, h, w)
+        self.label_name = label_name
+        aug = dict(random_resized_crop=bool(random_resized_crop),
+                   min_random_area=float(min_random_area),
+                   max_random_area=float(max_random_area),
+                   min_aspect_ratio=-1.0 if min_aspect_ratio is None
+                   else float(min_aspect_ratio),
+                   max_aspect_ratio=float(max_aspect_ratio),
+                   min_crop_size=int(min_crop_size),
+                   max_crop_size=int(max_crop_size), pad=int(pad),
+                   fill_value=float(fill_value), brightness=float(brightness),
+                   contrast=float(contrast), saturation=float(saturation),
+                   pca_noise=float(pca_noise))
+        off = dict(random_resized_crop=False, min_random_area=1.0,
+                   max_random_area=1.0, min_aspect_ratio=-1.0,
+                   max_aspect_ratio=0.0, min_crop_size=-1, max_crop_size=-1,
+                   pad=0, fill_value=255.0, brightness=0.0, contrast=0.0,
+                   saturation=0.0, pca_noise=0.0)
+        self._staged = aug != off or device is not None
+        self._dtype = torch.float32
+        if self._staged:
+            self._init_staged(ext, aug, dict(
+                batch_size=batch_size, part_index=part_index,
+                num_parts=num_parts, shuffle=shuffle,
+                num_threads=preprocess_threads, queue_capacity=prefetch_buffer,
+                seed=seed), rand_crop, rand_mirror, resize,
+                (mean_r, mean_g, mean_b), (std_r, std_g, std_b), device, dtype,
+                prefetch_to_device)
+            return
+        if dtype is not None:
+            raise ValueError("ImageRecordIter: dtype needs the staged path "
+                             "(pass device or an augmentation flag)")
         self._loader = ext.RecordBatchLoader(
             self._reader, batch_size, [h, w, c], part_index, num_parts,
             shuffle, preprocess_threads, prefetch_buffer, seed,
@@ -423,18 +507,104 @@ class ImageRecordIter(DataIter):
         else:
             self._mean = self._std = None
 
+    def _init_staged(self, ext, aug, loader_args, rand_crop, rand_mirror, resize,
+                     mean, std, device, dtype, prefetch_to_device):
+        c, h, w = self._chw
+        if c != 3:
+            raise ValueError("ImageRecordIter: data_shape[0] must be 3 on the "
+                             "staged path (1-channel records are not implemented)")
+        if (aug["min_crop_size"] == -1) != (aug["max_crop_size"] == -1) or \
+                aug["min_crop_size"] > aug["max_crop_size"] or \
+                (aug["min_crop_size"] != -1 and aug["min_crop_size"] < 1):
+            raise ValueError("ImageRecordIter: min_crop_size and max_crop_size "
+                             "must be set together, 1 <= min <= max")
+        if aug["min_random_area"] > aug["max_random_area"] or \
+                aug["min_random_area"] <= 0:
+            raise ValueError("ImageRecordIter: need 0 < min_random_area <= "
+                             "max_random_area")
+        lo = aug["min_aspect_ratio"]
+        lo, hi = (1 - aug["max_aspect_ratio"], 1 + aug["max_aspect_ratio"]) \
+            if lo < 0 else (lo, aug["max_aspect_ratio"])
+        if lo <= 0 or lo > hi:
+            raise ValueError("ImageRecordIter: need 0 < min_aspect_ratio <= "
+                             "max_aspect_ratio")
+        self._device = torch.device(device) if device is not None else torch.device("cpu")
+        on_gpu = self._device.type == "cuda"
+        self._dtype = dtype or (torch.bfloat16 if on_gpu else torch.float32)
+        self._mean = torch.tensor(mean, dtype=torch.float32)
+        self._std = torch.tensor(std, dtype=torch.float32)
+        if bool((self._std == 0).any()):
+            raise ValueError("ImageRecordIter: std_r, std_g, std_b must be != 0")
+        aug.update(th=h, tw=w, resize=int(resize), rand_crop=bool(rand_crop),
+                   rand_mirror=bool(rand_mirror))
+        self._loader = ext.RecordBatchLoader(self._reader, aug=aug, pin=on_gpu,
+                                             **loader_args)
+        self._stream = torch.cuda.Stream(self._device) \
+            if on_gpu and prefetch_to_device else None
+        self._pending = None    # batch k+1, issued on the private stream
+        self._inflight = []     # (event, pinned staging tensors) not yet done
+
+    def _issue(self):
+        """Take the next staged batch from the workers and augment it: on the
+        CPU, on the current stream, or on the private stream. -> (data, label,
+        event or None), or None at the end of the epoch."""
+        from dtmx.io.augment import augment_batch
+
+        out = self._loader.next()
+        if not out:
+            return None
+        src, geom, par, label = out
+        _, h, w = self._chw
+        if self._device.type != "cuda":
+            return augment_batch(src, geom, par, self._mean, self._std, h, w,
+                                 self._dtype), label, None
+        stream = self._stream or torch.cuda.current_stream(self._device)
+        with torch.cuda.stream(stream):
+            dev = [t.to(self._device, non_blocking=True) for t in out]
+            data = augment_batch(dev[0], dev[1], dev[2], self._mean, self._std,
+                                 h, w, self._dtype, geom_host=geom, par_host=par)
+            event = torch.cuda.Event()
+            event.record(stream)
+        # the pinned staging tensors outlive their copies
+        self._inflight = [(e, t) for e, t in self._inflight if not e.query()]
+        self._inflight.append((event, out))
+        return data, dev[3], event if self._stream is not None else None
+
+    def _next_staged(self):
+        cur = self._pending or self._issue()
+        self._pending = None
+        if cur is None:
+            raise StopIteration
+        data, label, event = cur
+        if event is not None:
+            self._pending = self._issue()
+            now = torch.cuda.current_stream(self._device)
+            now.wait_event(event)
+            data.record_stream(now)
+            label.record_stream(now)
+        return DataBatch(data=[data], label=[label], pad=0,
+                         provide_data=self.provide_data,
+                         provide_label=self.provide_label)
+
     @property
     def provide_data(self):
-        return [DataDesc("data", (self.batch_size,) + self._chw, torch.float32)]
+        return [DataDesc("data", (self.batch_size,) + self._chw, self._dtype)]
 
     @property
     def provide_label(self):
         return [DataDesc(self.label_name, (self.batch_size,), torch.float32)]
 
     def reset(self):
+        if self._staged:
+            if self._stream is not None:
+                self._stream.synchronize()
+            self._pending = None
+            self._inflight = [(e, t) for e, t in self._inflight if not e.query()]
         self._loader.reset()
 
     def next(self):
+        if self._staged:
+            return self._next_staged()
         out = self._loader.next()
         if not out:
             raise StopIteration

@@ -22,7 +22,8 @@ Engine / debugging:
   DTMX_FALLBACK         comma list of ops forced onto the torch reference
                         path: conv, dwconv (depthwise 3x3), gconv (grouped
                         3x3), bn, pool, avgpool (windowed average pool), gap,
-                        relu, lrn, linear, softmax, take, deconv
+                        relu, lrn, linear, softmax, take, deconv, augment
+                        (io.augment.augment_batch)
   DTMX_CHECK            1 = extra numerics checks in the op wrappers
   DTMX_PRINT_MEM        1 = print peak HBM use after bench
   DTMX_SEED / DTMX_TEST_SEED   RNG seeds (dtmx.random / tests)

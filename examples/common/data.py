@@ -26,7 +26,67 @@ def add_data_args(parser):
     data.add_argument("--random-mirror", type=int, default=1)
     data.add_argument("--resize", type=int, default=0,
                       help="resize shorter side before crop (0 = off)")
+    # the reference's add_data_aug_args names; any of them selects the
+    # iterator's staged path (decode on the CPU, augment on the device)
+    data.add_argument("--random-resized-crop", type=int, default=0)
+    data.add_argument("--min-random-area", type=float, default=1.0)
+    data.add_argument("--max-random-area", type=float, default=1.0)
+    data.add_argument("--min-random-aspect-ratio", type=float, default=None)
+    data.add_argument("--max-random-aspect-ratio", type=float, default=0.0)
+    data.add_argument("--brightness", type=float, default=0.0)
+    data.add_argument("--contrast", type=float, default=0.0)
+    data.add_argument("--saturation", type=float, default=0.0)
+    data.add_argument("--pca-noise", type=float, default=0.0)
+    data.add_argument("--pad-size", type=int, default=0)
+    data.add_argument("--fill-value", type=int, default=255)
+    data.add_argument("--min-crop-size", type=int, default=-1)
+    data.add_argument("--max-crop-size", type=int, default=-1)
+    data.add_argument("--rgb-mean", type=str, default="0,0,0",
+                      help="per-channel mean in 0-255 levels, e.g. 123.68,116.779,103.939")
+    data.add_argument("--rgb-std", type=str, default="1,1,1",
+                      help="per-channel std in 0-255 levels (1,1,1 = off)")
     return data
+
+
+_AUG_OFF = dict(random_resized_crop=False, min_random_area=1.0,
+                max_random_area=1.0, min_aspect_ratio=None, max_aspect_ratio=0.0,
+                brightness=0.0, contrast=0.0, saturation=0.0, pca_noise=0.0,
+                pad=0, fill_value=255, min_crop_size=-1, max_crop_size=-1)
+
+
+def _aug_kwargs(args, train):
+    """ImageRecordIter arguments from the augmentation flags. mean/std apply to
+    both iterators, the random augmenters to the training one. With any of
+    them set and --gpus given, batches are produced on the first GPU of the
+    module's context in the training dtype."""
+    kw = {}
+    mean = [float(v) for v in getattr(args, "rgb_mean", "0,0,0").split(",")]
+    std = [float(v) for v in getattr(args, "rgb_std", "1,1,1").split(",")]
+    if mean != [0.0] * 3 or std != [1.0] * 3:
+        # levels -> the iterator's [0,1] units; std 1,1,1 stays "off"
+        std = [1.0 if s == 1.0 else s / 255.0 for s in std]
+        kw.update(zip(("mean_r", "mean_g", "mean_b"), (m / 255.0 for m in mean)))
+        kw.update(zip(("std_r", "std_g", "std_b"), std))
+    if train:
+        aug = dict(
+            random_resized_crop=bool(getattr(args, "random_resized_crop", 0)),
+            min_random_area=getattr(args, "min_random_area", 1.0),
+            max_random_area=getattr(args, "max_random_area", 1.0),
+            min_aspect_ratio=getattr(args, "min_random_aspect_ratio", None),
+            max_aspect_ratio=getattr(args, "max_random_aspect_ratio", 0.0),
+            brightness=getattr(args, "brightness", 0.0),
+            contrast=getattr(args, "contrast", 0.0),
+            saturation=getattr(args, "saturation", 0.0),
+            pca_noise=getattr(args, "pca_noise", 0.0),
+            pad=getattr(args, "pad_size", 0),
+            fill_value=getattr(args, "fill_value", 255),
+            min_crop_size=getattr(args, "min_crop_size", -1),
+            max_crop_size=getattr(args, "max_crop_size", -1))
+        kw.update({k: v for k, v in aug.items() if v != _AUG_OFF[k]})
+    if any(k in _AUG_OFF for k in kw) and getattr(args, "gpus", None):
+        kw["device"] = "cuda:%d" % int(args.gpus.split(",")[0])
+        kw["dtype"] = getattr(torch, getattr(args, "dtype", "float32"))
+    return kw
 
 
 def _synthetic_pair(args, kv, image_shape, device=None, dtype=torch.float32):
@@ -54,16 +114,17 @@ def get_rec_iter(args, kv):
             args.data_train, image_shape, args.batch_size, shuffle=True,
             part_index=kv.rank, num_parts=kv.num_workers,
             preprocess_threads=args.data_nthreads,
-            rand_crop=bool(getattr(args, "random_crop", 1)),
+            rand_crop=bool(getattr(args, "random_crop", 1))
+            and not getattr(args, "random_resized_crop", 0),
             rand_mirror=bool(getattr(args, "random_mirror", 1)),
-            resize=getattr(args, "resize", 0),
+            resize=getattr(args, "resize", 0), **_aug_kwargs(args, True),
         )
         val = None
         if args.data_val and os.path.exists(args.data_val):
             val = ImageRecordIter(
                 args.data_val, image_shape, args.batch_size,
                 preprocess_threads=args.data_nthreads,
-                resize=getattr(args, "resize", 0),
+                resize=getattr(args, "resize", 0), **_aug_kwargs(args, False),
             )
         return train, val
     if args.data_train.endswith(".npz") and os.path.exists(args.data_train):

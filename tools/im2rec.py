@@ -7,6 +7,11 @@ HWC behind the reference IRHeader (flag,label,id,id2):
     python tools/im2rec.py out.rec --from-npz data.npz          # x:[N,H,W,C] u8, y:[N]
     python tools/im2rec.py out.rec --synthetic N H W C CLASSES  # random data
     python tools/im2rec.py out.rec --synthetic ... --jpeg --quality 90
+    python tools/im2rec.py out.rec --synthetic ... --raw-size   # id2 = (H << 32) | W
+
+With --raw-size a raw record names its own size in the header's id2 field, so
+the staged ImageRecordIter path takes raw records of any size (the fp32 path
+reads raw records of the target shape only).
 """
 import argparse
 import os
@@ -18,8 +23,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 
-def pack_record(label: float, raw: bytes, idx: int) -> bytes:
-    header = struct.pack("<IfQQ", 0, float(label), idx, 0)
+def pack_record(label: float, raw: bytes, idx: int, id2: int = 0) -> bytes:
+    header = struct.pack("<IfQQ", 0, float(label), idx, id2)
     return header + raw
 
 
@@ -32,6 +37,8 @@ def main():
     ap.add_argument("--jpeg", action="store_true",
                     help="JPEG-encode payloads (reference im2rec default)")
     ap.add_argument("--quality", type=int, default=95)
+    ap.add_argument("--raw-size", action="store_true",
+                    help="raw 3-channel records carry (H << 32) | W in id2")
     args = ap.parse_args()
     from dtmx.ops.hip import require_ext
 
@@ -50,7 +57,8 @@ def main():
                                                      args.quality), i)
                    for i in range(len(x))]
     else:
-        records = [pack_record(y[i], x[i].tobytes(), i) for i in range(len(x))]
+        id2 = (x.shape[1] << 32 | x.shape[2]) if args.raw_size else 0
+        records = [pack_record(y[i], x[i].tobytes(), i, id2) for i in range(len(x))]
     ext.write_recordio(args.out, records)
     print(f"wrote {len(records)} records to {args.out}")
 
