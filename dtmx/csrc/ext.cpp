@@ -13,6 +13,9 @@ at::Tensor conv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, lo
 at::Tensor conv_wgrad_nt256(const at::Tensor&, const at::Tensor&, long, long, long,
                             long, long, bool);
 std::tuple<bool, long, bool> wgrad_nt256_plan(long, long, long);
+std::tuple<long, long, long, long, long> gemm_plan(long, long, long, long, bool);
+std::tuple<bool, long> smallgrid_plan(long, long, long);
+std::tuple<long, long, long, bool, long, long> wgrad_nt_plan(long, long, long);
 at::Tensor conv_wgrad_acc32(const at::Tensor&, const at::Tensor&, long, long, long,
                             long, bool, long, bool);
 std::vector<at::Tensor> conv_dgrad_bnfuse(const at::Tensor&, const at::Tensor&,
@@ -151,6 +154,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // (use, splitk, group) the routing picks for a (Ko, RSC, NPQ) wgrad
   m.def("wgrad_nt256_plan", &dtmx::wgrad_nt256_plan, py::arg("Ko"),
         py::arg("RSC"), py::arg("NPQ"));
+  // Read-only routing plans (the launchers call the same functions):
+  // gemm_plan -> (kernel, tiles_m, tiles_n, slices, K-tiles per slice) with
+  // kernel 256 = gemm256f_kernel, 4 / 2 = gemm_tn_kernel<4> / <2>; lds_stage
+  // is false for the fp32-atomic (split-K) epilogue.
+  m.def("gemm_plan", &dtmx::gemm_plan, py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("splitk") = 1, py::arg("lds_stage") = true);
+  // (taken, splitk) of the small-grid fp32-atomic detour of conv fwd/dgrad
+  m.def("smallgrid_plan", &dtmx::smallgrid_plan, py::arg("M"), py::arg("N"),
+        py::arg("K"));
+  // (wm, nj, depth, grouped, slices, K-tiles per slice) of the gemm_nt_kernel
+  // launch for a wgrad that wgrad_nt256_plan does not claim
+  m.def("wgrad_nt_plan", &dtmx::wgrad_nt_plan, py::arg("Ko"), py::arg("RSC"),
+        py::arg("NPQ"));
   m.def("dwconv_fwd", &dtmx::dwconv_fwd, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("pad"));
   m.def("dwconv_dgrad", &dtmx::dwconv_dgrad, py::arg("dy"), py::arg("w"),

@@ -838,9 +838,15 @@ void gemm256f_kernel(PA pa, PB pb, EPI epi, uint32_t ktiles, uint32_t tiles_n) {
           }
         }
       }
-      float* red = (float*)ct;  // chunk reads done after the next barrier
-      epi_colreduce_write<NC8, 512>(red, db, epi.bnb_pdb, bmh, bn, epi.N, t);
-      epi_colreduce_write<NC8, 512>(red, dg, epi.bnb_pdg, bmh, bn, epi.N, t);
+      // The slabs are [ceil(M/128)][N]: when M % 256 is in [1, 128] the
+      // h = 1 half of the last M-tile starts at bmh >= M and its slab row
+      // bmh >> 7 == ceil(M/128) does not exist. Block-uniform, so the
+      // barriers inside stay legal.
+      if (bmh < epi.M) {
+        float* red = (float*)ct;  // chunk reads done after the next barrier
+        epi_colreduce_write<NC8, 512>(red, db, epi.bnb_pdb, bmh, bn, epi.N, t);
+        epi_colreduce_write<NC8, 512>(red, dg, epi.bnb_pdg, bmh, bn, epi.N, t);
+      }
     } else if constexpr (EPI::kFwdStats) {
       float s[8] = {}, ss[8] = {};
       for (uint32_t idx = t; idx < CHUNKS; idx += 512) {
@@ -867,9 +873,11 @@ void gemm256f_kernel(PA pa, PB pb, EPI epi, uint32_t ktiles, uint32_t tiles_n) {
           }
         }
       }
-      float* red = (float*)ct;
-      epi_colreduce_write<NC8, 512>(red, s, epi.bn_psum, bmh, bn, epi.N, t);
-      epi_colreduce_write<NC8, 512>(red, ss, epi.bn_psumsq, bmh, bn, epi.N, t);
+      if (bmh < epi.M) {  // no slab row for a half past M (see EpiBnBwd above)
+        float* red = (float*)ct;
+        epi_colreduce_write<NC8, 512>(red, s, epi.bn_psum, bmh, bn, epi.N, t);
+        epi_colreduce_write<NC8, 512>(red, ss, epi.bn_psumsq, bmh, bn, epi.N, t);
+      }
     } else {
       for (uint32_t idx = t; idx < CHUNKS; idx += 512) {
         uint32_t row = idx / NC8;
@@ -1719,22 +1727,46 @@ static hipStream_t cur_stream() {
 // pipelined K%64==0, 128-row slab granularity preserved). Dense AND gather
 // providers (conv fwd/dgrad A) are supported; OOB k pieces read the zero
 // page via the provider's own bounds checks on the gather side.
-template <class PA, class PB, class EPI>
-static bool try_gemm256(const PA& pa, const PB& pb, const EPI& epi,
-                        uint32_t M, uint32_t N, uint32_t K, uint32_t splitk) {
-  if constexpr (!EPI::kLdsStage) {
-    return false;
-  } else {
-    static const bool off = env_flag("DTMX_DISABLE_GEMM256");
-    if (off || splitk > 1) return false;
-    if (M < 512 || N < 192 || K < 128 || K % 64 != 0) return false;
+//
+// The routing decision itself is host-only and shared with the read-only
+// gemm_plan binding, so a test can assert which kernel a shape reaches.
+// kernel: 256 = gemm256f_kernel, 4 / 2 = gemm_tn_kernel<4> / <2>.
+struct GemmPlan {
+  int kernel;
+  uint32_t tiles_m, tiles_n;
+  uint32_t nslices, kt_per;  // split-K slices and K-tiles per slice
+};
+
+static bool gemm256_disabled() {
+  static const bool off = env_flag("DTMX_DISABLE_GEMM256");
+  return off;
+}
+
+static GemmPlan gemm_plan_of(uint32_t M, uint32_t N, uint32_t K,
+                             uint32_t splitk, bool lds_stage) {
+  if (lds_stage && !gemm256_disabled() && splitk <= 1 && M >= 512 &&
+      N >= 192 && K >= 128 && K % 64 == 0) {
     uint32_t tiles_m = ceil_div(M, 256), tiles_n = ceil_div(N, 256);
-    if (tiles_m * tiles_n < 160) return false;  // underfilled grid
-    dim3 grid(tiles_m * tiles_n);
-    gemm256f_kernel<PA, PB, EPI><<<grid, 512, 0, cur_stream()>>>(
-        pa, pb, epi, K / 64, tiles_n);
-    return true;
+    if (tiles_m * tiles_n >= 160)  // below: underfilled grid
+      return {256, tiles_m, tiles_n, 1, K / 64};
   }
+  uint32_t ktiles_total = ceil_div(K, 64);
+  splitk = std::min(splitk, ktiles_total);
+  uint32_t kt_per = ceil_div(ktiles_total, splitk);
+  uint32_t nslices = ceil_div(ktiles_total, kt_per);
+  uint32_t tiles_m = ceil_div(M, 128);
+  if (N <= 64)  // narrow-N tile: BN=64
+    return {2, tiles_m, ceil_div(N, 64), nslices, kt_per};
+  return {4, tiles_m, ceil_div(N, 128), nslices, kt_per};
+}
+
+std::tuple<long, long, long, long, long> gemm_plan(long M, long N, long K,
+                                                   long splitk, bool lds_stage) {
+  TORCH_CHECK(M > 0 && N > 0 && K > 0 && splitk >= 1, "gemm_plan: bad shape");
+  GemmPlan p = gemm_plan_of((uint32_t)M, (uint32_t)N, (uint32_t)K,
+                            (uint32_t)splitk, lds_stage);
+  return {(long)p.kernel, (long)p.tiles_m, (long)p.tiles_n, (long)p.nslices,
+          (long)p.kt_per};
 }
 
 // small grids underfill 256 CUs: callers pass want_splitk=true to let the
@@ -1742,28 +1774,38 @@ static bool try_gemm256(const PA& pa, const PB& pb, const EPI& epi,
 template <class PA, class PB, class EPI>
 static void launch_gemm(const PA& pa, const PB& pb, const EPI& epi, uint32_t M,
                         uint32_t N, uint32_t K, uint32_t splitk = 1) {
-  if (try_gemm256(pa, pb, epi, M, N, K, splitk)) return;
+  const GemmPlan p = gemm_plan_of(M, N, K, splitk, EPI::kLdsStage);
+  if (p.kernel == 256) {
+    if constexpr (EPI::kLdsStage) {
+      dim3 grid(p.tiles_m * p.tiles_n);
+      gemm256f_kernel<PA, PB, EPI><<<grid, 512, 0, cur_stream()>>>(
+          pa, pb, epi, p.kt_per, p.tiles_n);
+    }
+    return;
+  }
   uint32_t ktiles_total = ceil_div(K, 64);
-  splitk = std::min(splitk, ktiles_total);
-  uint32_t kt_per = ceil_div(ktiles_total, splitk);
-  uint32_t tiles_m = ceil_div(M, 128);
-  if (N <= 64) {  // narrow-N tile: BN=64
-    uint32_t tiles_n = ceil_div(N, 64);
-    dim3 grid(tiles_m * tiles_n, ceil_div(ktiles_total, kt_per));
+  dim3 grid(p.tiles_m * p.tiles_n, p.nslices);
+  if (p.kernel == 2) {
     gemm_tn_kernel<2, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
-        pa, pb, epi, ktiles_total, tiles_n, kt_per);
+        pa, pb, epi, ktiles_total, p.tiles_n, p.kt_per);
   } else {
-    uint32_t tiles_n = ceil_div(N, 128);
-    dim3 grid(tiles_m * tiles_n, ceil_div(ktiles_total, kt_per));
     gemm_tn_kernel<4, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
-        pa, pb, epi, ktiles_total, tiles_n, kt_per);
+        pa, pb, epi, ktiles_total, p.tiles_n, p.kt_per);
   }
 }
 
-template <class PA, class PB, class EPI>
-static void launch_gemm_nt(const PA& pa, const PB& pb, const EPI& epi,
-                           uint32_t M, uint32_t N, uint32_t K,
-                           uint32_t splitk = 1) {
+// Routing of launch_gemm_nt, host-only and shared with the read-only
+// wgrad_nt_plan binding. Tile class (wm, nj): (1, 4) flat 64x256, (2, 2)
+// 128x64 for N <= 64, (2, 4) 128x128; (1, 2) is the DTMX_NT_WM1NJ2 probe.
+struct NtPlan {
+  uint32_t wm, nj, depth;
+  bool group;  // XCD-grouped 1-D launch
+  uint32_t tiles_m, tiles_n;
+  uint32_t nslices, kt_per;
+};
+
+static NtPlan gemm_nt_plan_of(uint32_t M, uint32_t N, uint32_t K,
+                              uint32_t splitk) {
   uint32_t ktiles_total = ceil_div(K, 64);
   splitk = std::min(splitk, ktiles_total);
   uint32_t kt_per = ceil_div(ktiles_total, splitk);
@@ -1801,6 +1843,8 @@ static void launch_gemm_nt(const PA& pa, const PB& pb, const EPI& epi,
     kt_per = ceil_div(ktiles_total, ns8);
     nslices = ceil_div(ktiles_total, kt_per);
   }
+  const uint32_t depth = depth3 ? 3 : 2;
+  const bool grouped = group && !depth3;
   if (M <= 64 && N > 64) {
     // flat 64x256 tile: ResNet's K_out=64 wgrads waste half the 128-row
     // tile on zero rows (see gemm_nt_kernel WM doc)
@@ -1810,56 +1854,49 @@ static void launch_gemm_nt(const PA& pa, const PB& pb, const EPI& epi,
       const char* v = getenv("DTMX_NT_WM1NJ2");
       return v && v[0] == '1';
     }();
-    if (wm1nj2) {
-      uint32_t tiles_n = ceil_div(N, 128);
-      dim3 grid(tiles_n, nslices);
-      gemm_nt_kernel<2, 1, 2, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
-          pa, pb, epi, ktiles_total, tiles_n, kt_per);
-      return;
-    }
-    uint32_t tiles_n = ceil_div(N, 256);
-    dim3 grid(tiles_n, nslices);
-    if (group && !depth3)
-      gemm_nt_kernel<4, 1, 2, PA, PB, EPI, 1>
-          <<<8 * tiles_n * ceil_div(nslices, 8u), 256, 0, cur_stream()>>>(
-              pa, pb, epi, ktiles_total, tiles_n, kt_per, tiles_n);
-    else if (depth3)
-      gemm_nt_kernel<4, 1, 3, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
-          pa, pb, epi, ktiles_total, tiles_n, kt_per);
-    else
-      gemm_nt_kernel<4, 1, 2, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
-          pa, pb, epi, ktiles_total, tiles_n, kt_per);
-    return;
+    if (wm1nj2) return {1, 2, 2, false, 1, ceil_div(N, 128), nslices, kt_per};
+    return {1, 4, depth, grouped, 1, ceil_div(N, 256), nslices, kt_per};
   }
   uint32_t tiles_m = ceil_div(M, 128);
-  if (N <= 64) {
-    uint32_t tiles_n = ceil_div(N, 64);
-    dim3 grid(tiles_m * tiles_n, nslices);
-    if (group && !depth3)
-      gemm_nt_kernel<2, 2, 2, PA, PB, EPI, 1>
-          <<<8 * tiles_m * tiles_n * ceil_div(nslices, 8u), 256, 0,
-             cur_stream()>>>(pa, pb, epi, ktiles_total, tiles_n, kt_per,
-                             tiles_m * tiles_n);
-    else if (depth3)
-      gemm_nt_kernel<2, 2, 3, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
-          pa, pb, epi, ktiles_total, tiles_n, kt_per);
-    else
-      gemm_nt_kernel<2, 2, 2, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
-          pa, pb, epi, ktiles_total, tiles_n, kt_per);
+  if (N <= 64)
+    return {2, 2, depth, grouped, tiles_m, ceil_div(N, 64), nslices, kt_per};
+  return {2, 4, depth, grouped, tiles_m, ceil_div(N, 128), nslices, kt_per};
+}
+
+// one tile class of launch_gemm_nt: grouped, depth-3 or the default launch
+template <int NJ, int WM, class PA, class PB, class EPI>
+static void launch_gemm_nt_tile(const NtPlan& p, const PA& pa, const PB& pb,
+                                const EPI& epi, uint32_t ktiles_total) {
+  const uint32_t tiles = p.tiles_m * p.tiles_n;
+  dim3 grid(tiles, p.nslices);
+  if (p.group)
+    gemm_nt_kernel<NJ, WM, 2, PA, PB, EPI, 1>
+        <<<8 * tiles * ceil_div(p.nslices, 8u), 256, 0, cur_stream()>>>(
+            pa, pb, epi, ktiles_total, p.tiles_n, p.kt_per, tiles);
+  else if (p.depth == 3)
+    gemm_nt_kernel<NJ, WM, 3, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
+        pa, pb, epi, ktiles_total, p.tiles_n, p.kt_per);
+  else
+    gemm_nt_kernel<NJ, WM, 2, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
+        pa, pb, epi, ktiles_total, p.tiles_n, p.kt_per);
+}
+
+template <class PA, class PB, class EPI>
+static void launch_gemm_nt(const PA& pa, const PB& pb, const EPI& epi,
+                           uint32_t M, uint32_t N, uint32_t K,
+                           uint32_t splitk = 1) {
+  const NtPlan p = gemm_nt_plan_of(M, N, K, splitk);
+  const uint32_t ktiles_total = ceil_div(K, 64);
+  if (p.wm == 1 && p.nj == 2) {
+    dim3 grid(p.tiles_n, p.nslices);
+    gemm_nt_kernel<2, 1, 2, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
+        pa, pb, epi, ktiles_total, p.tiles_n, p.kt_per);
+  } else if (p.wm == 1) {
+    launch_gemm_nt_tile<4, 1>(p, pa, pb, epi, ktiles_total);
+  } else if (p.nj == 2) {
+    launch_gemm_nt_tile<2, 2>(p, pa, pb, epi, ktiles_total);
   } else {
-    uint32_t tiles_n = ceil_div(N, 128);
-    dim3 grid(tiles_m * tiles_n, nslices);
-    if (group && !depth3)
-      gemm_nt_kernel<4, 2, 2, PA, PB, EPI, 1>
-          <<<8 * tiles_m * tiles_n * ceil_div(nslices, 8u), 256, 0,
-             cur_stream()>>>(pa, pb, epi, ktiles_total, tiles_n, kt_per,
-                             tiles_m * tiles_n);
-    else if (depth3)
-      gemm_nt_kernel<4, 2, 3, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
-          pa, pb, epi, ktiles_total, tiles_n, kt_per);
-    else
-      gemm_nt_kernel<4, 2, 2, PA, PB, EPI><<<grid, 256, 0, cur_stream()>>>(
-          pa, pb, epi, ktiles_total, tiles_n, kt_per);
+    launch_gemm_nt_tile<4, 2>(p, pa, pb, epi, ktiles_total);
   }
 }
 
@@ -1986,19 +2023,32 @@ static void conv_out_dims(uint32_t H, uint32_t W, uint32_t R, uint32_t S,
   Q = (W + 2 * pad - S) / stride + 1;
 }
 
+// the smallgrid_splitk predicate and its split-K (0 = plain launch);
+// host-only, shared with the read-only smallgrid_plan binding
+static uint32_t smallgrid_splitk_of(uint32_t M, uint32_t N, uint32_t K) {
+  uint32_t tiles = ceil_div(M, 128) * ceil_div(N, N <= 64 ? 64 : 128);
+  uint32_t ktiles = ceil_div(K, 64);
+  // only for severely underfilled grids: the fp32-atomic + cast overhead and
+  // the shortened per-block K loop beat plain launch only below ~160 blocks
+  // (measured: 392-block l3 conv lost 40%, 196-block l4 was a wash).
+  if (tiles >= 160 || ktiles < 8) return 0;
+  return std::min(ktiles / 4, std::max<uint32_t>(2, 1024 / tiles));
+}
+
+std::tuple<bool, long> smallgrid_plan(long M, long N, long K) {
+  TORCH_CHECK(M > 0 && N > 0 && K > 0, "smallgrid_plan: bad shape");
+  uint32_t splitk = smallgrid_splitk_of((uint32_t)M, (uint32_t)N, (uint32_t)K);
+  return {splitk != 0, (long)splitk};
+}
+
 // run a bf16-output GEMM through fp32 atomics + cast when its natural grid
 // underfills the chip (e.g. the 7x7 resnet stage: 196 blocks on 256 CUs).
 template <class PA, class PB>
 static bool smallgrid_splitk(const PA& pa, const PB& pb, at::Tensor& out_bf16,
                              uint32_t M, uint32_t N, uint32_t K) {
   using elem_t = typename PA::elem;
-  uint32_t tiles = ceil_div(M, 128) * ceil_div(N, N <= 64 ? 64 : 128);
-  uint32_t ktiles = ceil_div(K, 64);
-  // only for severely underfilled grids: the fp32-atomic + cast overhead and
-  // the shortened per-block K loop beat plain launch only below ~160 blocks
-  // (measured: 392-block l3 conv lost 40%, 196-block l4 was a wash).
-  if (tiles >= 160 || ktiles < 8) return false;
-  uint32_t splitk = std::min(ktiles / 4, std::max<uint32_t>(2, 1024 / tiles));
+  const uint32_t splitk = smallgrid_splitk_of(M, N, K);
+  if (!splitk) return false;
   auto acc = at::zeros({(long)M, (long)N}, out_bf16.options().dtype(at::kFloat));
   EpiAtomicF32<elem_t> epi{acc.data_ptr<float>(), M, N};
   launch_gemm(pa, pb, epi, M, N, K, splitk);
@@ -2081,9 +2131,7 @@ std::vector<at::Tensor> conv_fwd_stats(const at::Tensor& x, const at::Tensor& w,
     conv_out_dims(H, W_, R, S, stride, pad, P, Q);
     uint32_t M = N * P * Q, Ktot = R * S * C;
     uint32_t tiles_m = ceil_div(M, 128);
-    uint32_t tiles = tiles_m * ceil_div(Ko, Ko <= 64 ? 64 : 128);
-    uint32_t ktiles = ceil_div(Ktot, 64);
-    bool smallgrid = tiles < 160 && ktiles >= 8;  // mirrors smallgrid_splitk
+    const bool smallgrid = smallgrid_splitk_of(M, Ko, Ktot) != 0;
     if (C % 8 != 0 || smallgrid) {
       auto y = conv_fwd(x, w, stride, pad);
       auto empty = at::empty({0}, x.options().dtype(at::kFloat));
@@ -2373,6 +2421,38 @@ std::tuple<bool, long, bool> wgrad_nt256_plan(long Ko, long RSC, long NPQ) {
   return {use, (long)splitk, group};
 }
 
+// split-K that conv_wgrad hands to launch_gemm_nt when the 256² kernel is
+// not used (host-only; shared with the read-only wgrad_nt_plan binding)
+static uint32_t wgrad_nt_splitk_of(uint32_t Ko, uint32_t RSC, uint32_t NPQ) {
+  uint32_t tiles_mn =
+      (Ko <= 64 && RSC > 64)
+          ? ceil_div(RSC, 256)  // flat 64x256 tile (launch_gemm_nt)
+          : ceil_div(Ko, 128) * ceil_div(RSC, RSC <= 64 ? 64 : 128);
+  uint32_t ktiles = ceil_div(NPQ, 64);
+  static const uint32_t target_blocks = [] {
+    const char* v = getenv("DTMX_WGRAD_TARGET_BLOCKS");
+    // 512 = exactly 2 blocks/CU: the sweep 256..4096 measured 512 best
+    // on every wgrad shape (+25% over the old 1024 — no partial block
+    // wave, fewest split-K atomic passes that still fill the chip)
+    return v ? (uint32_t)atoi(v) : 512u;
+  }();
+  return std::max<uint32_t>(
+      1, std::min<uint32_t>(ktiles, target_blocks / std::max(1u, tiles_mn)));
+}
+
+// gemm_nt_kernel launch of a (Ko, RSC, NPQ) wgrad that does not take the
+// 256² kernel: (wm, nj, depth, XCD-grouped, slices, K-tiles per slice), with
+// (wm, nj) = (1, 4) flat 64x256, (2, 2) 128x64, (2, 4) 128x128 tile
+std::tuple<long, long, long, bool, long, long> wgrad_nt_plan(long Ko, long RSC,
+                                                             long NPQ) {
+  TORCH_CHECK(Ko > 0 && RSC > 0 && NPQ > 0, "wgrad_nt_plan: bad shape");
+  NtPlan p = gemm_nt_plan_of(
+      (uint32_t)Ko, (uint32_t)RSC, (uint32_t)NPQ,
+      wgrad_nt_splitk_of((uint32_t)Ko, (uint32_t)RSC, (uint32_t)NPQ));
+  return {(long)p.wm, (long)p.nj, (long)p.depth, p.group, (long)p.nslices,
+          (long)p.kt_per};
+}
+
 // transpose-free wgrad: dy and the im2col view of x are read NHWC-native by
 // the contraction-major (NT) kernels. use256 selects gemm256nt_kernel with
 // the given split-K / grouping; otherwise launch_gemm_nt routes as before.
@@ -2528,20 +2608,7 @@ at::Tensor conv_wgrad(const at::Tensor& x, const at::Tensor& dy, long R, long S,
                                       (uint32_t)std::get<1>(plan),
                                       std::get<2>(plan));
       }
-      uint32_t tiles_mn =
-          (Ko <= 64 && RSC > 64)
-              ? ceil_div(RSC, 256)  // flat 64x256 tile (launch_gemm_nt)
-              : ceil_div(Ko, 128) * ceil_div(RSC, RSC <= 64 ? 64 : 128);
-      uint32_t ktiles = ceil_div(M, 64);
-      static const uint32_t target_blocks = [] {
-        const char* v = getenv("DTMX_WGRAD_TARGET_BLOCKS");
-        // 512 = exactly 2 blocks/CU: the sweep 256..4096 measured 512 best
-        // on every wgrad shape (+25% over the old 1024 — no partial block
-        // wave, fewest split-K atomic passes that still fill the chip)
-        return v ? (uint32_t)atoi(v) : 512u;
-      }();
-      uint32_t splitk = std::max<uint32_t>(
-          1, std::min<uint32_t>(ktiles, target_blocks / std::max(1u, tiles_mn)));
+      const uint32_t splitk = wgrad_nt_splitk_of(Ko, RSC, M);
       return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, false, splitk,
                                   false);
     }
@@ -2606,7 +2673,7 @@ at::Tensor conv_wgrad(const at::Tensor& x, const at::Tensor& dy, long R, long S,
       return dwm.permute({0, 3, 1, 2});
     }
     auto dw = dw32.reshape({(long)Ko, (long)R, (long)S, (long)C})
-                  .to(at::kBFloat16)
+                  .to(x.scalar_type())
                   .permute({0, 3, 1, 2});
     return dw.contiguous(at::MemoryFormat::ChannelsLast);
 
