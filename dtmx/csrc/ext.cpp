@@ -10,6 +10,11 @@ at::Tensor conv_fwd(const at::Tensor&, const at::Tensor&, long, long);
 at::Tensor conv_dgrad(const at::Tensor&, const at::Tensor&, long, long, long, long,
                       const c10::optional<at::Tensor>&);
 at::Tensor conv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, long);
+at::Tensor conv_fwd_hw(const at::Tensor&, const at::Tensor&, long, long, long);
+at::Tensor conv_dgrad_hw(const at::Tensor&, const at::Tensor&, long, long, long,
+                         long, long);
+at::Tensor conv_wgrad_hw(const at::Tensor&, const at::Tensor&, long, long, long,
+                         long, long);
 at::Tensor conv_wgrad_nt256(const at::Tensor&, const at::Tensor&, long, long, long,
                             long, long, bool);
 std::tuple<bool, long, bool> wgrad_nt256_plan(long, long, long);
@@ -34,6 +39,9 @@ at::Tensor gconv_fwd(const at::Tensor&, const at::Tensor&, long, long, long);
 at::Tensor gconv_dgrad(const at::Tensor&, const at::Tensor&, long, long, long, long,
                        long);
 at::Tensor gconv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, bool);
+// lineconv.hip
+at::Tensor lineconv_fwd(const at::Tensor&, const at::Tensor&);
+at::Tensor lineconv_dgrad(const at::Tensor&, const at::Tensor&);
 // avgpool.hip
 at::Tensor avgpool_fwd(const at::Tensor&, long, long, long, bool);
 at::Tensor avgpool_bwd(const at::Tensor&, long, long, long, long, long, bool);
@@ -49,7 +57,7 @@ std::vector<at::Tensor> bn_fwd_train(const at::Tensor&, const at::Tensor&,
                                      const c10::optional<at::Tensor>&,
                                      const c10::optional<at::Tensor>&, bool);
 std::vector<at::Tensor> conv_fwd_stats(const at::Tensor&, const at::Tensor&,
-                                       long, long);
+                                       long, long, long);
 std::vector<at::Tensor> bn_local_sums(const at::Tensor&);
 std::vector<at::Tensor> bn_fwd_presummed(const at::Tensor&, const at::Tensor&,
                                          const at::Tensor&, at::Tensor,
@@ -138,11 +146,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_dgrad", &dtmx::linear_dgrad);
   m.def("linear_wgrad", &dtmx::linear_wgrad);
   m.def("conv_fwd", &dtmx::conv_fwd);
-  m.def("conv_fwd_stats", &dtmx::conv_fwd_stats);
+  // pad_w >= 0: per-axis form (pad is the H axis); a rectangular call
+  // returns empty slabs
+  m.def("conv_fwd_stats", &dtmx::conv_fwd_stats, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("pad"), py::arg("pad_w") = -1);
   m.def("conv_dgrad", &dtmx::conv_dgrad, py::arg("dy"), py::arg("w"),
         py::arg("stride"), py::arg("pad"), py::arg("H"), py::arg("W"),
         py::arg("acc") = c10::nullopt);
   m.def("conv_wgrad", &dtmx::conv_wgrad);
+  // Per-axis padding (pad_h, pad_w) and rectangular kernels on the plain
+  // paths: gather/dense fwd, dgrad, NT wgrad. C % 8 == 0 and Ko % 8 == 0.
+  m.def("conv_fwd_hw", &dtmx::conv_fwd_hw, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("pad_h"), py::arg("pad_w"));
+  m.def("conv_dgrad_hw", &dtmx::conv_dgrad_hw, py::arg("dy"), py::arg("w"),
+        py::arg("stride"), py::arg("pad_h"), py::arg("pad_w"), py::arg("H"),
+        py::arg("W"));
+  m.def("conv_wgrad_hw", &dtmx::conv_wgrad_hw, py::arg("x"), py::arg("dy"),
+        py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad_h"),
+        py::arg("pad_w"));
+  // 1xT / Tx1 (T in {3,5,7}), stride 1, same padding on the tap axis; w is
+  // the (Ko,C,1,T) or (Ko,C,T,1) channels_last parameter
+  m.def("lineconv_fwd", &dtmx::lineconv_fwd, py::arg("x"), py::arg("w"));
+  m.def("lineconv_dgrad", &dtmx::lineconv_dgrad, py::arg("dy"), py::arg("w"));
   // test/bench entry: always the 256² contraction-major kernel
   m.def("conv_wgrad_nt256", &dtmx::conv_wgrad_nt256, py::arg("x"),
         py::arg("dy"), py::arg("R"), py::arg("S"), py::arg("stride"),

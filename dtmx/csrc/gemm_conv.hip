@@ -2018,9 +2018,9 @@ at::Tensor linear_wgrad(const at::Tensor& dy, const at::Tensor& x) {
 // ------------------------------------------------------------- conv fwd
 
 static void conv_out_dims(uint32_t H, uint32_t W, uint32_t R, uint32_t S,
-                          int stride, int pad, uint32_t& P, uint32_t& Q) {
-  P = (H + 2 * pad - R) / stride + 1;
-  Q = (W + 2 * pad - S) / stride + 1;
+                          int stride, int ph, int pw, uint32_t& P, uint32_t& Q) {
+  P = (H + 2 * ph - R) / stride + 1;
+  Q = (W + 2 * pw - S) / stride + 1;
 }
 
 // the smallgrid_splitk predicate and its split-K (0 = plain launch);
@@ -2059,8 +2059,10 @@ static bool smallgrid_splitk(const PA& pa, const PB& pb, at::Tensor& out_bf16,
   return true;
 }
 
-at::Tensor conv_fwd(const at::Tensor& x, const at::Tensor& w, long stride,
-                    long pad) {
+// (ph, pw) = padding of the H and of the W axis; the public square forms
+// pass pad twice
+static at::Tensor conv_fwd_impl(const at::Tensor& x, const at::Tensor& w,
+                                long stride, long ph, long pw) {
   DTMX_DISPATCH_16(x.scalar_type(), "conv_fwd", {
     CHECK_BF16_CUDA(x);
     CHECK_BF16_CUDA(w);
@@ -2069,12 +2071,12 @@ at::Tensor conv_fwd(const at::Tensor& x, const at::Tensor& w, long stride,
     uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W_ = x.size(3);
     uint32_t Ko = w.size(0), R = w.size(2), S = w.size(3);
     uint32_t P, Q;
-    conv_out_dims(H, W_, R, S, stride, pad, P, Q);
+    conv_out_dims(H, W_, R, S, stride, ph, pw, P, Q);
     auto y = at::empty({(long)N, (long)Ko, (long)P, (long)Q},
                        x.options(), at::MemoryFormat::ChannelsLast);
     uint32_t M = N * P * Q, Ktot = R * S * C;
     EpiBF16<elem_t> epi{(elem_t*)y.data_ptr(), nullptr, M, Ko, 0};
-    if (R == 1 && S == 1 && stride == 1 && pad == 0 && C % 8 == 0) {
+    if (R == 1 && S == 1 && stride == 1 && ph == 0 && pw == 0 && C % 8 == 0) {
       // 1x1/s1: the im2col matrix IS x — pure dense GEMM, no gather decode
       DenseP<elem_t> pa{(const elem_t*)x.data_ptr(), zero_page<elem_t>(x), M, C, C};
       DenseP<elem_t> pb{(const elem_t*)w.data_ptr(), zero_page<elem_t>(x), Ko, C, C};
@@ -2086,7 +2088,7 @@ at::Tensor conv_fwd(const at::Tensor& x, const at::Tensor& w, long stride,
       pa.x = (const elem_t*)x.data_ptr();
       pa.zero = zero_page<elem_t>(x);
       pa.M = M; pa.Ktot = Ktot; pa.C = C; pa.H = H; pa.W = W_; pa.Q = Q; pa.S = S;
-      pa.u = stride; pa.v = stride; pa.ph = pad; pa.pw = pad;
+      pa.u = stride; pa.v = stride; pa.ph = ph; pa.pw = pw;
       pa.dQ.init(Q); pa.dPQ.init(P * Q); pa.dC.init(C); pa.dS.init(S);
       if (!smallgrid_splitk(pa, pb, y, M, Ko, Ktot))
         launch_gemm(pa, pb, epi, M, Ko, Ktot);
@@ -2100,7 +2102,7 @@ at::Tensor conv_fwd(const at::Tensor& x, const at::Tensor& w, long stride,
       uint32_t blocks = std::min<size_t>((total + 255) / 256, 16384);
       im2col_kernel<<<blocks, 256, 0, cur_stream()>>>(
           (const elem_t*)x.data_ptr(), (elem_t*)col.data_ptr(), M, Kpad, Ktot, C,
-          H, W_, Q, S, stride, stride, pad, pad, dQ, dPQ, dC, dS);
+          H, W_, Q, S, stride, stride, ph, pw, dQ, dPQ, dC, dS);
       // zero-pad the weight rows to Kpad so the k tail multiplies 0*0, not 0*NaN
       auto wpad = at::constant_pad_nd(
           w.permute({0, 2, 3, 1}).reshape({(long)Ko, (long)Ktot}),
@@ -2115,20 +2117,82 @@ at::Tensor conv_fwd(const at::Tensor& x, const at::Tensor& w, long stride,
   return at::Tensor();
 }
 
+at::Tensor conv_fwd(const at::Tensor& x, const at::Tensor& w, long stride,
+                    long pad) {
+  return conv_fwd_impl(x, w, stride, pad, pad);
+}
+
+// Envelope of the per-axis (*_hw) entries, which cover the plain paths only:
+// 16-bit NHWC activation `a` with `ach` channels, KRSC weight, C % 8 == 0 and
+// Ko % 8 == 0 (the fused BN epilogues and the C % 8 != 0 im2col stem stay
+// with the square forms), a window that fits the padded input.
+static void conv_hw_check(const char* op, const char* aname, const at::Tensor& a,
+                          const at::Tensor& w, bool a_is_dy, long stride,
+                          long ph, long pw, long H, long W_) {
+  TORCH_CHECK(a.is_cuda() && (a.scalar_type() == at::kBFloat16 ||
+                              a.scalar_type() == at::kHalf),
+              op, ": ", aname, " must be a GPU bfloat16/float16 tensor");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == a.scalar_type() &&
+                  w.device() == a.device(),
+              op, ": w must be on the device of ", aname, " and of its dtype");
+  TORCH_CHECK(a.dim() == 4 && a.numel() > 0 &&
+                  a.is_contiguous(at::MemoryFormat::ChannelsLast),
+              op, ": ", aname, " must be a non-empty 4-D NHWC (channels_last) tensor");
+  TORCH_CHECK(w.dim() == 4 && w.numel() > 0 &&
+                  w.is_contiguous(at::MemoryFormat::ChannelsLast),
+              op, ": w must be a non-empty 4-D KRSC (channels_last) tensor");
+  TORCH_CHECK(stride >= 1, op, ": stride must be >= 1, got ", stride);
+  TORCH_CHECK(ph >= 0 && pw >= 0, op, ": padding must be >= 0, got (", ph, ", ",
+              pw, ")");
+  const long Ko = w.size(0), C = w.size(1), R = w.size(2), S = w.size(3);
+  TORCH_CHECK(C % 8 == 0, op, ": C % 8 == 0 required, got C = ", C);
+  TORCH_CHECK(Ko % 8 == 0, op, ": Ko % 8 == 0 required, got Ko = ", Ko);
+  TORCH_CHECK(a.size(1) == (a_is_dy ? Ko : C), op, ": ", aname, " has ",
+              a.size(1), " channels, w wants ", a_is_dy ? Ko : C);
+  TORCH_CHECK(H > 0 && W_ > 0 && H + 2 * ph >= R && W_ + 2 * pw >= S, op,
+              ": the ", R, "x", S, " window does not fit the padded ", H, "x",
+              W_, " input");
+  TORCH_CHECK((uintptr_t)a.data_ptr() % 16 == 0, op, ": ", aname,
+              " must be 16-byte aligned");
+  const long P = (H + 2 * ph - R) / stride + 1, Q = (W_ + 2 * pw - S) / stride + 1;
+  TORCH_CHECK(a.size(0) * H * W_ * C < (1ll << 31) &&
+                  a.size(0) * P * Q * Ko < (1ll << 31) &&
+                  R * S * C * Ko < (1ll << 31),
+              op, ": x, y and w must each hold fewer than 2^31 elements");
+  if (a_is_dy)
+    TORCH_CHECK(a.size(2) == P && a.size(3) == Q, op, ": dy is ", a.size(2), "x",
+                a.size(3), ", the window gives ", P, "x", Q);
+}
+
+at::Tensor conv_fwd_hw(const at::Tensor& x, const at::Tensor& w, long stride,
+                       long ph, long pw) {
+  TORCH_CHECK(x.dim() == 4, "conv_fwd_hw: x must be a 4-D (N,C,H,W) tensor");
+  conv_hw_check("conv_fwd_hw", "x", x, w, false, stride, ph, pw, x.size(2),
+                x.size(3));
+  return conv_fwd_impl(x, w, stride, ph, pw);
+}
+
 // conv forward with fused BN statistics: returns (y, psum, psumsq) where the
 // slabs are [tiles_m][Ko] per-block column sums/sumsq of y (epilogue fusion —
 // the following BatchNorm skips its whole-tensor stats read). Returns empty
 // slabs when the shape routed through a non-fusable path; the caller falls
 // back to the standalone stats kernel.
+// pad_w >= 0 is the per-axis form (pad = the H axis): a rectangular call
+// (R != S or pad != pad_w) is such a non-fusable path.
 std::vector<at::Tensor> conv_fwd_stats(const at::Tensor& x, const at::Tensor& w,
-                                       long stride, long pad) {
+                                       long stride, long pad, long pad_w) {
+  if (pad_w >= 0 && (pad_w != pad || w.size(2) != w.size(3))) {
+    auto y = conv_fwd_hw(x, w, stride, pad, pad_w);
+    auto empty = at::empty({0}, x.options().dtype(at::kFloat));
+    return {y, empty, empty};
+  }
   DTMX_DISPATCH_16(x.scalar_type(), "conv_fwd_stats", {
     CHECK_BF16_CUDA(x);
     TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), "x must be NHWC");
     uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W_ = x.size(3);
     uint32_t Ko = w.size(0), R = w.size(2), S = w.size(3);
     uint32_t P, Q;
-    conv_out_dims(H, W_, R, S, stride, pad, P, Q);
+    conv_out_dims(H, W_, R, S, stride, pad, pad, P, Q);
     uint32_t M = N * P * Q, Ktot = R * S * C;
     uint32_t tiles_m = ceil_div(M, 128);
     const bool smallgrid = smallgrid_splitk_of(M, Ko, Ktot) != 0;
@@ -2170,9 +2234,9 @@ std::vector<at::Tensor> conv_fwd_stats(const at::Tensor& x, const at::Tensor& w,
 
 // ------------------------------------------------------------- conv dgrad
 
-at::Tensor conv_dgrad(const at::Tensor& dy, const at::Tensor& w, long stride,
-                      long pad, long H, long W_,
-                      const c10::optional<at::Tensor>& acc) {
+static at::Tensor conv_dgrad_impl(const at::Tensor& dy, const at::Tensor& w,
+                                  long stride, long ph, long pw, long H, long W_,
+                                  const c10::optional<at::Tensor>& acc) {
   DTMX_DISPATCH_16(dy.scalar_type(), "conv_dgrad", {
     CHECK_BF16_CUDA(dy);
     TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast), "dy must be NHWC");
@@ -2220,7 +2284,7 @@ at::Tensor conv_dgrad(const at::Tensor& dy, const at::Tensor& w, long stride,
                      at::MemoryFormat::ChannelsLast);
     }
     uint32_t M = N * H * W_, Ktot = R * S * Ko;
-    if (R == 1 && S == 1 && pad == 0 && C % 8 == 0) {
+    if (R == 1 && S == 1 && ph == 0 && pw == 0 && C % 8 == 0) {
       // 1x1 dgrad: dense dy @ W^T. Stride 1 writes rows directly; stride u>1
       // scatters row (n,p,q) to pixel (n, p*u, q*v) of a zeroed dx — the
       // gathered formulation wastes 1-1/u^2 of its blocks on all-zero rows
@@ -2249,7 +2313,7 @@ at::Tensor conv_dgrad(const at::Tensor& dy, const at::Tensor& w, long stride,
     pa.dy = (const elem_t*)dyc.data_ptr();
     pa.zero = zero_page<elem_t>(dy);
     pa.M = M; pa.Ktot = Ktot; pa.Ko = Ko; pa.H = H; pa.W = W_; pa.P = P; pa.Q = Q;
-    pa.S = S; pa.u = stride; pa.v = stride; pa.ph = pad; pa.pw = pad;
+    pa.S = S; pa.u = stride; pa.v = stride; pa.ph = ph; pa.pw = pw;
     pa.dW_.init(W_); pa.dHW.init(H * W_); pa.dKo.init(Ko); pa.dS.init(S);
     DenseP<elem_t> pb{(const elem_t*)wt.data_ptr(), zero_page<elem_t>(dy), C, Ktot, Ktot};
     EpiBF16<elem_t> epi{(elem_t*)dx.data_ptr(), nullptr, M, C, 0};
@@ -2260,6 +2324,18 @@ at::Tensor conv_dgrad(const at::Tensor& dy, const at::Tensor& w, long stride,
 
   });
   return at::Tensor();
+}
+
+at::Tensor conv_dgrad(const at::Tensor& dy, const at::Tensor& w, long stride,
+                      long pad, long H, long W_,
+                      const c10::optional<at::Tensor>& acc) {
+  return conv_dgrad_impl(dy, w, stride, pad, pad, H, W_, acc);
+}
+
+at::Tensor conv_dgrad_hw(const at::Tensor& dy, const at::Tensor& w, long stride,
+                         long ph, long pw, long H, long W_) {
+  conv_hw_check("conv_dgrad_hw", "dy", dy, w, true, stride, ph, pw, H, W_);
+  return conv_dgrad_impl(dy, w, stride, ph, pw, H, W_, c10::nullopt);
 }
 
 // conv dgrad with the BN-backward epilogue fusion (EpiBnBwd): computes
@@ -2458,7 +2534,7 @@ std::tuple<long, long, long, bool, long, long> wgrad_nt_plan(long Ko, long RSC,
 // the given split-K / grouping; otherwise launch_gemm_nt routes as before.
 template <typename elem_t>
 static at::Tensor wgrad_nt_run(const at::Tensor& x, const at::Tensor& dy,
-                               long R, long S, long stride, long pad,
+                               long R, long S, long stride, long ph, long pw,
                                bool use256, uint32_t splitk, bool group,
                                bool want_f32 = false) {
   uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W_ = x.size(3);
@@ -2478,7 +2554,7 @@ static at::Tensor wgrad_nt_run(const at::Tensor& x, const at::Tensor& dy,
   pb.x = (const elem_t*)x.data_ptr();
   pb.zero = zero_page<elem_t>(x);
   pb.Kd = M; pb.Ndim = RSC; pb.C = C; pb.H = H; pb.W = W_; pb.Q = Q; pb.S = S;
-  pb.u = stride; pb.v = stride; pb.ph = pad; pb.pw = pad;
+  pb.u = stride; pb.v = stride; pb.ph = ph; pb.pw = pw;
   pb.dQ.init(Q); pb.dPQ.init(P * Q); pb.dC.init(C); pb.dS.init(S);
   EpiAtomicF32<elem_t> epi{dw32.data_ptr<float>(), Ko, RSC};
   if (use256)
@@ -2544,7 +2620,7 @@ at::Tensor conv_wgrad_nt256(const at::Tensor& x, const at::Tensor& dy, long R,
               "conv_wgrad_nt256: 1 <= splitk <= ceil(N*P*Q / 64) required, "
               "got splitk = ", splitk, " with ", ktiles, " K-tiles");
   DTMX_DISPATCH_16(x.scalar_type(), "conv_wgrad_nt256", {
-    return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, true,
+    return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, pad, true,
                                 (uint32_t)splitk, group);
   });
   return at::Tensor();
@@ -2566,7 +2642,7 @@ at::Tensor conv_wgrad_acc32(const at::Tensor& x, const at::Tensor& dy, long R,
   const uint32_t M = x.size(0) * dy.size(2) * dy.size(3);
   DTMX_DISPATCH_16(x.scalar_type(), "conv_wgrad_acc32", {
     if (nt256)
-      return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, true,
+      return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, pad, true,
                                   (uint32_t)splitk, group, true);
     uint32_t tiles_mn =
         (Ko <= 64 && RSC > 64)
@@ -2574,14 +2650,14 @@ at::Tensor conv_wgrad_acc32(const at::Tensor& x, const at::Tensor& dy, long R,
             : ceil_div(Ko, 128) * ceil_div(RSC, RSC <= 64 ? 64 : 128);
     uint32_t old_splitk = std::max<uint32_t>(
         1, std::min<uint32_t>(ceil_div(M, 64), 512 / std::max(1u, tiles_mn)));
-    return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, false, old_splitk,
-                                false, true);
+    return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, pad, false,
+                                old_splitk, false, true);
   });
   return at::Tensor();
 }
 
-at::Tensor conv_wgrad(const at::Tensor& x, const at::Tensor& dy, long R, long S,
-                      long stride, long pad) {
+static at::Tensor conv_wgrad_impl(const at::Tensor& x, const at::Tensor& dy,
+                                  long R, long S, long stride, long ph, long pw) {
   DTMX_DISPATCH_16(x.scalar_type(), "conv_wgrad", {
     CHECK_BF16_CUDA(x);
     CHECK_BF16_CUDA(dy);
@@ -2604,12 +2680,12 @@ at::Tensor conv_wgrad(const at::Tensor& x, const at::Tensor& dy, long R, long S,
             (uintptr_t)x.data_ptr() % 16 == 0 &&
             (uintptr_t)dy.data_ptr() % 16 == 0;
         if (std::get<0>(plan) && envelope)
-          return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, true,
+          return wgrad_nt_run<elem_t>(x, dy, R, S, stride, ph, pw, true,
                                       (uint32_t)std::get<1>(plan),
                                       std::get<2>(plan));
       }
       const uint32_t splitk = wgrad_nt_splitk_of(Ko, RSC, M);
-      return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, false, splitk,
+      return wgrad_nt_run<elem_t>(x, dy, R, S, stride, ph, pw, false, splitk,
                                   false);
     }
 
@@ -2627,7 +2703,7 @@ at::Tensor conv_wgrad(const at::Tensor& x, const at::Tensor& dy, long R, long S,
           Im2colRows<elem_t> rows;
           rows.x = (const elem_t*)x.data_ptr();
           rows.M = M; rows.C = C; rows.H = H; rows.W = W_; rows.Q = Q;
-          rows.u = stride; rows.v = stride; rows.ph = pad; rows.pw = pad;
+          rows.u = stride; rows.v = stride; rows.ph = ph; rows.pw = pw;
           rows.r = r; rows.s = s;
           rows.dQ.init(Q); rows.dPQ.init(P * Q);
           transpose_rowgather_kernel<Im2colRows<elem_t>>
@@ -2644,7 +2720,7 @@ at::Tensor conv_wgrad(const at::Tensor& x, const at::Tensor& dy, long R, long S,
       uint32_t blocks = std::min<size_t>((total + 255) / 256, 16384);
       im2col_kernel<<<blocks, 256, 0, cur_stream()>>>(
           (const elem_t*)x.data_ptr(), (elem_t*)col.data_ptr(), M, Kpad, RSC, C,
-          H, W_, Q, S, stride, stride, pad, pad, dQ, dPQ, dC, dS);
+          H, W_, Q, S, stride, stride, ph, pw, dQ, dPQ, dC, dS);
       xt = transpose2d<elem_t>(col, Mpad).narrow(0, 0, RSC).contiguous();
     }
 
@@ -2679,6 +2755,45 @@ at::Tensor conv_wgrad(const at::Tensor& x, const at::Tensor& dy, long R, long S,
 
   });
   return at::Tensor();
+}
+
+at::Tensor conv_wgrad(const at::Tensor& x, const at::Tensor& dy, long R, long S,
+                      long stride, long pad) {
+  return conv_wgrad_impl(x, dy, R, S, stride, pad, pad);
+}
+
+// per-axis wgrad: always the NT kernels (C % 8 == 0 and Ko % 8 == 0)
+at::Tensor conv_wgrad_hw(const at::Tensor& x, const at::Tensor& dy, long R, long S,
+                         long stride, long ph, long pw) {
+  const char* op = "conv_wgrad_hw";
+  TORCH_CHECK(x.is_cuda() && dy.is_cuda() &&
+                  (x.scalar_type() == at::kBFloat16 ||
+                   x.scalar_type() == at::kHalf) &&
+                  dy.scalar_type() == x.scalar_type() && dy.device() == x.device(),
+              op, ": x and dy must be GPU tensors of one 16-bit dtype and device");
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4 && x.numel() > 0 && dy.numel() > 0 &&
+                  x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  dy.is_contiguous(at::MemoryFormat::ChannelsLast),
+              op, ": x and dy must be non-empty 4-D NHWC (channels_last) tensors");
+  TORCH_CHECK(R >= 1 && S >= 1 && stride >= 1 && ph >= 0 && pw >= 0, op,
+              ": bad window (R, S, stride >= 1; padding >= 0)");
+  const long N = x.size(0), C = x.size(1), H = x.size(2), W_ = x.size(3);
+  const long Ko = dy.size(1);
+  TORCH_CHECK(C % 8 == 0, op, ": C % 8 == 0 required, got C = ", C);
+  TORCH_CHECK(Ko % 8 == 0, op, ": Ko % 8 == 0 required, got Ko = ", Ko);
+  TORCH_CHECK(H + 2 * ph >= R && W_ + 2 * pw >= S, op, ": the ", R, "x", S,
+              " window does not fit the padded ", H, "x", W_, " input");
+  const long P = (H + 2 * ph - R) / stride + 1, Q = (W_ + 2 * pw - S) / stride + 1;
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == P && dy.size(3) == Q, op,
+              ": dy shape does not match x and the window (want ", N, "x", Ko,
+              "x", P, "x", Q, ")");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                  (uintptr_t)dy.data_ptr() % 16 == 0,
+              op, ": x and dy must be 16-byte aligned");
+  TORCH_CHECK(N * H * W_ * C < (1ll << 31) && N * P * Q * Ko < (1ll << 31) &&
+                  R * S * C * Ko < (1ll << 31),
+              op, ": x, dy and dw must each hold fewer than 2^31 elements");
+  return conv_wgrad_impl(x, dy, R, S, stride, ph, pw);
 }
 
 }  // namespace dtmx

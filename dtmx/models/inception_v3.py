@@ -65,6 +65,28 @@ class InceptionC(nn.Module):
         return torch.cat([self.b1(x), self.b2(x), self.b3(x), self.b4(x)], dim=1)
 
 
+class InceptionCF(nn.Module):
+    """The reference's Inception7C: 1x7 / 7x1 factorised towers. Submodule
+    order follows the reference's tower / tower_1 layer order."""
+
+    def __init__(self, in_ch, ch7):
+        super().__init__()
+        h, v = ((1, 7), (0, 3)), ((7, 1), (3, 0))  # (kernel, pad)
+        self.b1 = ConvBN(in_ch, 192, 1)
+        self.b2 = nn.Sequential(ConvBN(in_ch, ch7, 1),
+                                ConvBN(ch7, ch7, h[0], 1, h[1]),
+                                ConvBN(ch7, 192, v[0], 1, v[1]))
+        self.b3 = nn.Sequential(ConvBN(in_ch, ch7, 1),
+                                ConvBN(ch7, ch7, v[0], 1, v[1]),
+                                ConvBN(ch7, ch7, h[0], 1, h[1]),
+                                ConvBN(ch7, ch7, v[0], 1, v[1]),
+                                ConvBN(ch7, 192, h[0], 1, h[1]))
+        self.b4 = nn.Sequential(_AvgPool3s1(), ConvBN(in_ch, 192, 1))
+
+    def forward(self, x):
+        return torch.cat([self.b1(x), self.b2(x), self.b3(x), self.b4(x)], dim=1)
+
+
 class InceptionD(nn.Module):
     def __init__(self, in_ch):
         super().__init__()
@@ -77,20 +99,39 @@ class InceptionD(nn.Module):
         return torch.cat([self.b1(x), self.b2(x), self.pool(x)], dim=1)
 
 
-class InceptionE(nn.Module):
-    """The E block's 3x3 branches split into two parallel convs whose outputs
-    concatenate (1x3/3x1 in the original; square 3x3 here), so the block
-    emits 320+768+768+192 = 2048 channels."""
+class InceptionDF(nn.Module):
+    """The reference's Inception7D: 1x7 / 7x1 ahead of the stride-2 3x3."""
 
     def __init__(self, in_ch):
         super().__init__()
+        self.b1 = nn.Sequential(ConvBN(in_ch, 192, 1), ConvBN(192, 320, 3, 2, 0))
+        self.b2 = nn.Sequential(ConvBN(in_ch, 192, 1),
+                                ConvBN(192, 192, (1, 7), 1, (0, 3)),
+                                ConvBN(192, 192, (7, 1), 1, (3, 0)),
+                                ConvBN(192, 192, 3, 2, 0))
+        self.pool = MaxPool2dNHWC(3, 2, 0)
+
+    def forward(self, x):
+        return torch.cat([self.b1(x), self.b2(x), self.pool(x)], dim=1)
+
+
+class InceptionE(nn.Module):
+    """The E block's 3x3 branches split into two parallel convs whose outputs
+    concatenate (1x3/3x1 in the original; square 3x3 here), so the block
+    emits 320+768+768+192 = 2048 channels. factorized: the reference's
+    Inception7E, whose four parallel convs are 1x3 / 3x1."""
+
+    def __init__(self, in_ch, factorized=False):
+        super().__init__()
+        ka, pa, kb, pb = ((1, 3), (0, 1), (3, 1), (1, 0)) if factorized \
+            else (3, 1, 3, 1)
         self.b1 = ConvBN(in_ch, 320, 1)
         self.b2a = ConvBN(in_ch, 384, 1)
-        self.b2b1 = ConvBN(384, 384, 3, 1, 1)
-        self.b2b2 = ConvBN(384, 384, 3, 1, 1)
+        self.b2b1 = ConvBN(384, 384, ka, 1, pa)
+        self.b2b2 = ConvBN(384, 384, kb, 1, pb)
         self.b3 = nn.Sequential(ConvBN(in_ch, 448, 1), ConvBN(448, 384, 3, 1, 1))
-        self.b3b1 = ConvBN(384, 384, 3, 1, 1)
-        self.b3b2 = ConvBN(384, 384, 3, 1, 1)
+        self.b3b1 = ConvBN(384, 384, ka, 1, pa)
+        self.b3b2 = ConvBN(384, 384, kb, 1, pb)
         self.b4 = nn.Sequential(_AvgPool3s1(), ConvBN(in_ch, 192, 1))
 
     def forward(self, x):
@@ -105,9 +146,14 @@ class InceptionE(nn.Module):
 
 
 class InceptionV3(nn.Module):
-    def __init__(self, num_classes=1000):
+    """factorized=True: blocks C, D and E carry the reference's 1x7 / 7x1 and
+    1x3 / 3x1 layers (its parameter shapes); the default keeps the square 3x3
+    stand-ins."""
+
+    def __init__(self, num_classes=1000, factorized=False):
         super().__init__()
         self.spec = {"network": "inception-v3", "num_classes": num_classes}
+        C, D = (InceptionCF, InceptionDF) if factorized else (InceptionC, InceptionD)
         self.stem = nn.Sequential(
             ConvBN(3, 32, 3, 2, 0), ConvBN(32, 32, 3, 1, 0), ConvBN(32, 64, 3, 1, 1),
             MaxPool2dNHWC(3, 2, 0),
@@ -116,10 +162,9 @@ class InceptionV3(nn.Module):
         self.blocks = nn.Sequential(
             InceptionA(192, 32), InceptionA(256, 64), InceptionA(288, 64),
             InceptionB(288),
-            InceptionC(768, 128), InceptionC(768, 160), InceptionC(768, 160),
-            InceptionC(768, 192),
-            InceptionD(768),
-            InceptionE(1280), InceptionE(2048),
+            C(768, 128), C(768, 160), C(768, 160), C(768, 192),
+            D(768),
+            InceptionE(1280, factorized), InceptionE(2048, factorized),
         )
         self.pool = GlobalAvgPool()
         self.fc = LinearBF16(2048, num_classes)
@@ -131,5 +176,5 @@ class InceptionV3(nn.Module):
         return self.fc(x)
 
 
-def get_symbol(num_classes=1000, **kwargs):
-    return InceptionV3(num_classes=num_classes)
+def get_symbol(num_classes=1000, factorized=False, **kwargs):
+    return InceptionV3(num_classes=num_classes, factorized=factorized)

@@ -7,6 +7,7 @@ Compute dtype bf16 (fp32 accumulate inside kernels); CPU path is fp32 torch.
 
 Reference kernel parity:
   conv fwd/dgrad/wgrad   <- src/operator/nn/convolution.cu (cuDNN/im2col)
+  1xT / Tx1 line conv    <- src/operator/nn/convolution.cu (kernel=(1,7), ...)
   depthwise 3x3 conv     <- src/operator/nn/depthwise_convolution_tf.cuh
   grouped 3x3 conv       <- src/operator/nn/convolution.cu (num_group > 1)
   batch_norm fwd/bwd     <- src/operator/nn/batch_norm.cu:208-360
@@ -80,10 +81,117 @@ class _ConvNHWC(torch.autograd.Function):
         return dx, dw, None, None, None
 
 
-def conv2d(x, w, stride: int = 1, padding: int = 0, want_stats: bool = False):
-    """want_stats: also return the fused per-block BN statistic slabs
+class _ConvHWNHWC(torch.autograd.Function):
+    """Per-axis padding (ph, pw) and rectangular kernels on the generic
+    gather / NT kernels (the *_hw entries)."""
+
+    @staticmethod
+    def forward(ctx, x, w, stride, ph, pw):
+        ctx.save_for_backward(x, w)
+        ctx.conv = (stride, ph, pw)
+        return require_ext().conv_fwd_hw(x, w, stride, ph, pw)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = require_ext()
+        x, w = ctx.saved_tensors
+        stride, ph, pw = ctx.conv
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.conv_dgrad_hw(dy, w, stride, ph, pw, x.shape[2], x.shape[3])
+        if ctx.needs_input_grad[1]:
+            dw = ext.conv_wgrad_hw(x, dy, w.shape[2], w.shape[3], stride, ph, pw)
+        return dx, dw, None, None, None
+
+
+class _LineConvNHWC(torch.autograd.Function):
+    """1xT / Tx1 same-padded stride-1 conv on the lineconv.hip kernels (fwd,
+    dgrad); wgrad runs the generic NT kernels."""
+
+    @staticmethod
+    def forward(ctx, x, w, ph, pw):
+        ctx.save_for_backward(x, w)
+        ctx.pad = (ph, pw)
+        return require_ext().lineconv_fwd(x, w)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = require_ext()
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.lineconv_dgrad(dy, w)
+        if ctx.needs_input_grad[1]:
+            dw = ext.conv_wgrad_hw(x, dy, w.shape[2], w.shape[3], 1, *ctx.pad)
+        return dx, dw, None, None
+
+
+def _lineconv_in_envelope(x, w, stride, ph, pw) -> bool:
+    """The cases lineconv.hip implements: 1xT or Tx1 with T in {3, 5, 7},
+    stride 1, padding (T-1)/2 on the tap axis and 0 on the other, C % 8 == 0,
+    Ko % 8 == 0, a 16-byte aligned x, N*H*W < 2^31 and, for Tx1, a halo
+    (T-1)*W of at most 256 rows."""
+    if x.dim() != 4 or w.dim() != 4 or stride != 1:
+        return False
+    Ko, C, R, S = w.shape
+    if (R == 1) == (S == 1):
+        return False
+    T, vertical = max(R, S), S == 1
+    pad = (T - 1) // 2
+    return (T in (3, 5, 7) and (ph, pw) == ((pad, 0) if vertical else (0, pad))
+            and x.shape[1] == C and C % 8 == 0 and Ko % 8 == 0
+            and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31
+            and w.numel() < 2 ** 31
+            and (not vertical or (T - 1) * x.shape[3] <= 256)
+            and w.dtype == x.dtype
+            and w.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0)
+
+
+def _lineconv_routed(x, w, stride, ph, pw) -> bool:
+    """In the envelope and in a shape class where the line kernel measured
+    faster than the generic gather path (tools/bench_lineconv.py, profiles/
+    inception_mi355x.md): every 1xT, and Tx1 while the window fits 160 rows
+    ((T-1)*W <= 32, two blocks per CU). The 17x17 7x1 layers lost 6-26 %."""
+    if not _lineconv_in_envelope(x, w, stride, ph, pw):
+        return False
+    return w.shape[3] != 1 or (w.shape[2] - 1) * x.shape[3] <= 32
+
+
+def conv2d(x, w, stride: int = 1, padding=0, want_stats: bool = False):
+    """padding: an int, or an (h, w) pair; the kernel shape is read from w.
+
+    A square call with int padding takes the dense / gather kernels with
+    their fused epilogues. 1xT / Tx1 same-padded stride-1 calls take the line
+    kernels where those measured faster (_lineconv_routed; DTMX_FALLBACK=
+    lineconv: the generic per-axis path); every other rectangular or per-axis
+    call takes the generic per-axis path.
+
+    want_stats: also return the fused per-block BN statistic slabs
     (psum, psumsq) computed in the conv epilogue — the following BatchNorm
-    then skips its own whole-tensor stats pass."""
+    then skips its own whole-tensor stats pass. The slabs are empty where the
+    path does not fuse them (every per-axis call)."""
+    if not isinstance(padding, int):
+        ph, pw = (int(p) for p in padding)
+        padding = ph if ph == pw and w.shape[2] == w.shape[3] else (ph, pw)
+    if _use_hip(x, op="conv") and not isinstance(padding, int):
+        C = x.shape[1]
+        if C % 8 != 0:
+            padc = 8 - (C % 8)
+            x = F.pad(x, (0, 0, 0, 0, 0, padc))
+            w = F.pad(w, (0, 0, 0, 0, 0, padc))
+        x = x.contiguous(memory_format=torch.channels_last)
+        w = w.contiguous(memory_format=torch.channels_last)
+        if "lineconv" not in _FALLBACK and _lineconv_routed(x, w, stride, ph, pw):
+            y = _LineConvNHWC.apply(x, w, ph, pw)
+        else:
+            y = _ConvHWNHWC.apply(x, w, stride, ph, pw)
+        if want_stats:
+            z = y.new_zeros(0, dtype=torch.float32)
+            return y, z, z
+        return y
     if _use_hip(x, op="conv"):
         C = x.shape[1]
         if C % 8 != 0:
@@ -102,6 +210,9 @@ def conv2d(x, w, stride: int = 1, padding: int = 0, want_stats: bool = False):
         if want_stats:
             return y, ps, pss
         return y
+    if want_stats and not isinstance(padding, int):
+        y = F.conv2d(x, w, None, stride, padding)
+        return y, y.new_zeros(0), y.new_zeros(0)
     return F.conv2d(x, w, None, stride, padding)
 
 

@@ -16,15 +16,26 @@ from . import functional as DF
 
 
 class Conv2dNHWC(nn.Module):
+    """kernel_size and padding: an int, or an (h, w) pair (the reference's
+    kernel=(1, 7), pad=(0, 3)); the weight is (Ko, C, R, S)."""
+
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0,
                  bias=False):
         super().__init__()
         self.in_channels = in_channels
         self.out_channels = out_channels
+        if isinstance(kernel_size, int):
+            kh = kw = kernel_size
+        else:
+            kh, kw = kernel_size = tuple(int(k) for k in kernel_size)
+            if isinstance(padding, int):
+                padding = (padding, padding)
+        if not isinstance(padding, int):
+            padding = tuple(int(p) for p in padding)
         self.kernel_size = kernel_size
         self.stride = stride
         self.padding = padding
-        w = torch.empty(out_channels, in_channels, kernel_size, kernel_size)
+        w = torch.empty(out_channels, in_channels, kh, kw)
         nn.init.kaiming_normal_(w, mode="fan_in", nonlinearity="relu")
         self.weight = nn.Parameter(w)
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
