@@ -18,6 +18,11 @@ at::Tensor conv_wgrad_hw(const at::Tensor&, const at::Tensor&, long, long, long,
 at::Tensor conv_wgrad_nt256(const at::Tensor&, const at::Tensor&, long, long, long,
                             long, long, bool);
 std::tuple<bool, long, bool> wgrad_nt256_plan(long, long, long);
+at::Tensor conv_wgrad_narrow(const at::Tensor&, const at::Tensor&, long, long, long,
+                             long, long, bool);
+at::Tensor conv_wgrad_narrow_acc32(const at::Tensor&, const at::Tensor&, long, long,
+                                   long, long, long, bool);
+std::tuple<bool, std::string, long, bool> wgrad_narrow_plan(long, long, long);
 std::tuple<long, long, long, long, long> gemm_plan(long, long, long, long, bool);
 std::tuple<bool, long> smallgrid_plan(long, long, long);
 std::tuple<long, long, long, bool, long, long> wgrad_nt_plan(long, long, long);
@@ -178,6 +183,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pad"), py::arg("nt256"), py::arg("splitk"), py::arg("group"));
   // (use, splitk, group) the routing picks for a (Ko, RSC, NPQ) wgrad
   m.def("wgrad_nt256_plan", &dtmx::wgrad_nt256_plan, py::arg("Ko"),
+        py::arg("RSC"), py::arg("NPQ"));
+  // test/bench entry: always the streaming narrow-tile kernel (Ko <= 128 or
+  // R*S*C <= 128), and its fp32 split-K sums before the 16-bit rounding
+  m.def("conv_wgrad_narrow", &dtmx::conv_wgrad_narrow, py::arg("x"),
+        py::arg("dy"), py::arg("R"), py::arg("S"), py::arg("stride"),
+        py::arg("pad"), py::arg("splitk"), py::arg("group"));
+  m.def("conv_wgrad_narrow_acc32", &dtmx::conv_wgrad_narrow_acc32,
+        py::arg("x"), py::arg("dy"), py::arg("R"), py::arg("S"),
+        py::arg("stride"), py::arg("pad"), py::arg("splitk"), py::arg("group"));
+  // (use, tile class "64x256" / "128x256" / "256x128" / "256x64" or "",
+  // splitk, group) the routing picks for a (Ko, RSC, NPQ) wgrad
+  m.def("wgrad_narrow_plan", &dtmx::wgrad_narrow_plan, py::arg("Ko"),
         py::arg("RSC"), py::arg("NPQ"));
   // Read-only routing plans (the launchers call the same functions):
   // gemm_plan -> (kernel, tiles_m, tiles_n, slices, K-tiles per slice) with

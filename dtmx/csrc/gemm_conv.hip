@@ -1517,6 +1517,267 @@ void gemm256nt_kernel(PA pa, PB pb, EPI epi, uint32_t ktiles_total,
   epi.store(acc, bm + am_half * 128, bn + wc, lane);
 }
 
+// ---------------------- streaming narrow-tile NT kernel (contraction-major)
+// gemm256nt_kernel's operands, Col/Row staging contexts and transposed LDS
+// reads on tiles whose narrow side is 64 or 128 columns: AW x BW (M x N) is
+// 64x256, 128x256, 256x128 or 256x64, so the narrow operand is read once and
+// the wide one half as often as with the 128-wide tiles of gemm_nt_kernel.
+// 512 threads, one block per CU, BK = 64. A wave owns a 64x64 output tile
+// (acc[4][4]); the 64-wide tiles have four of those, and their eight waves
+// split each K-tile's two 32-row halves between them (both halves add into
+// the fp32 output atomically, like two more split-K slices).
+//
+// LDS: a ring of DEPTH = 3 K-tile buffers, each the A image followed by the B
+// image. An image is one [64 kd][64 cols] part (128-byte rows) or one / two
+// [64 kd][128 cols] parts (256-byte rows): 40 KiB per K-tile on the 64-wide
+// tiles (ring 120 KiB), 48 KiB on the 128-wide ones (ring 144 KiB).
+//
+// Staging: one glds16 of the block covers 64 (64-col part) or 32 (128-col
+// part) kd rows; thread (wave w, lane l) stages LDS piece l % PPR of row
+// g*RPI + w*RPW + l / PPR. Its column piece is fixed for the kernel (Col
+// context), its rows are decoded once per K-tile and shared by the parts of
+// an operand (Row context). Every thread issues L = 5 or 6 loads per K-tile.
+//
+// Swizzle, in 32-byte chunks (the run one kd row contributes to a
+// ds_read_b64_tr_b16 block): LDS chunk c of row k holds source chunk
+// c ^ fc(k). A 32-lane read half covers rows {k0..k0+3, k0+8..k0+11} of one
+// chunk column. With 256-byte rows all eight sit on the same 8 banks:
+// fc = (k & 3) | ((k >> 3) & 1) << 2 sends them to the eight different
+// chunks of a row. With 128-byte rows even and odd rows already differ:
+// fc = ((k >> 1) & 1) | ((k >> 3) & 1) << 1. Row bit 2 (the lo / hi read of
+// a fragment) is not used, so hi = lo + 4 rows. fc is constant per staging
+// thread (row bits 0..3 do not depend on g) and per reading lane.
+//
+// Issue order and waits (per thread, tile kt of the slice):
+//   prologue            stage tile 0, stage tile 1
+//   top of tile kt      s_waitcnt vmcnt(L) (tile kt+1 may be in flight;
+//                       vmcnt(0) when there is no tile kt+1), s_barrier
+//   then                issue the ds_reads of tile kt's first half, stage
+//                       tile kt+2 into buffer (kt+2) % 3, MFMAs
+// so two whole K-tiles beyond the one being computed are in flight. Buffer
+// (kt+2) % 3 last held tile kt-1: every wave retired its reads of it
+// (lgkmcnt(0) before its last MFMAs) before arriving at the barrier of tile
+// kt, and the restage is issued after that barrier.
+// GROUP: the XCD-grouped 1-D launch of gemm_nt_kernel.
+template <int WD>
+struct NtsImg {
+  static constexpr uint32_t PW = WD < 128 ? WD : 128;  // part width, columns
+  static constexpr uint32_t PARTS = WD / PW;
+  static constexpr uint32_t PPR = PW / 8;   // 16-byte pieces per row
+  static constexpr uint32_t RPW = 64 / PPR;  // kd rows of one wave's glds16
+  static constexpr uint32_t RPI = 8 * RPW;   // ... of the block's
+  static constexpr uint32_t G = 64 / RPI;    // glds16 per thread and part
+  static constexpr uint32_t ROWB = PW * 2;   // bytes per LDS row
+  // chunk swizzle from row bits (0,1) = lo2 and row bit 3 = b3
+  static __device__ __forceinline__ uint32_t fc(uint32_t lo2, uint32_t b3) {
+    return PPR == 16 ? (lo2 | (b3 << 2)) : ((lo2 >> 1) | (b3 << 1));
+  }
+};
+
+template <int AW, int BW, class PA, class PB, class EPI, int GROUP = 0>
+__launch_bounds__(512) __global__
+void gemm_nts_kernel(PA pa, PB pb, EPI epi, uint32_t ktiles_total,
+                     uint32_t tiles_n, uint32_t kt_per_slice,
+                     uint32_t tiles_total) {
+  using elem_t = typename PA::elem;
+  using V8 = typename E8<elem_t>::v8;
+  using IA = NtsImg<AW>;
+  using IB = NtsImg<BW>;
+  typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_;
+  union Frag {
+    V8 f;
+    u32x2_ h[2];
+  };
+  constexpr uint32_t DEPTH = 3;
+  constexpr uint32_t TILE = 64 * (AW + BW);  // elements per K-tile buffer
+  constexpr uint32_t B_OFF = 64 * AW;
+  constexpr uint32_t NWT = (AW / 64) * (BW / 64);  // 64x64 wave tiles
+  static_assert(NWT == 4 || NWT == 8, "tile must hold 4 or 8 wave tiles");
+  constexpr uint32_t KSPLIT = 8 / NWT;  // waves per wave tile (K halves)
+  constexpr uint32_t L = IA::G * IA::PARTS + IB::G * IB::PARTS;
+  static_assert(DEPTH * TILE * 2 <= 144 * 1024, "ring exceeds 144 KiB");
+  uint32_t slice, bid;
+  if constexpr (GROUP) {
+    const uint32_t xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+    bid = j % tiles_total;
+    slice = xcd + 8 * (j / tiles_total);
+  } else {
+    bid = xcd_swizzle(blockIdx.x, gridDim.x);
+    slice = blockIdx.y;
+  }
+  const uint32_t kt0 = slice * kt_per_slice;
+  if (kt0 >= ktiles_total) return;  // block-uniform, before any barrier
+  const uint32_t ktiles = min(kt_per_slice, ktiles_total - kt0);
+  __shared__ __attribute__((aligned(16))) elem_t smem[DEPTH * TILE];
+  const uint32_t t = threadIdx.x;
+  const uint32_t wave = t >> 6, lane = t & 63;
+  const uint32_t bm = (bid / tiles_n) * AW, bn = (bid % tiles_n) * BW;
+
+  // ---- staging contexts
+  const uint32_t srow_a = wave * IA::RPW + lane / IA::PPR;  // + g*RPI
+  const uint32_t srow_b = wave * IB::RPW + lane / IB::PPR;
+  const uint32_t spiece_a =
+      (lane % IA::PPR) ^ (IA::fc(srow_a & 3, (srow_a >> 3) & 1) << 1);
+  const uint32_t spiece_b =
+      (lane % IB::PPR) ^ (IB::fc(srow_b & 3, (srow_b >> 3) & 1) << 1);
+  typename PA::Col acol[IA::PARTS];
+  typename PB::Col bcol[IB::PARTS];
+#pragma unroll
+  for (uint32_t h = 0; h < IA::PARTS; ++h)
+    acol[h] = pa.col((bm >> 3) + h * 16 + spiece_a);
+#pragma unroll
+  for (uint32_t h = 0; h < IB::PARTS; ++h)
+    bcol[h] = pb.col((bn >> 3) + h * 16 + spiece_b);
+  auto stage = [&](uint32_t buf, uint32_t kt) {
+    elem_t* base = smem + buf * TILE;
+    const uint64_t kd0 = (uint64_t)(kt0 + kt) * 64;
+#pragma unroll
+    for (uint32_t g = 0; g < IA::G; ++g) {
+      const typename PA::Row row = pa.row(kd0 + g * IA::RPI + srow_a);
+#pragma unroll
+      for (uint32_t h = 0; h < IA::PARTS; ++h)
+        glds16(pa.addr(row, acol[h]),
+               base + h * 8192 + (g * IA::RPI + wave * IA::RPW) * IA::PW);
+    }
+#pragma unroll
+    for (uint32_t g = 0; g < IB::G; ++g) {
+      const typename PB::Row row = pb.row(kd0 + g * IB::RPI + srow_b);
+#pragma unroll
+      for (uint32_t h = 0; h < IB::PARTS; ++h)
+        glds16(pb.addr(row, bcol[h]),
+               base + B_OFF + h * 8192 +
+                   (g * IB::RPI + wave * IB::RPW) * IB::PW);
+    }
+  };
+
+  stage(0, 0);
+  if (ktiles > 1) stage(1, 1);
+
+  // ---- fragment read addresses (bytes, inside K-tile buffer 0). Source
+  // lane r_ of a 16-lane group supplies row kbase + r_/4, bytes (r_%4)*8 of
+  // the block's chunk; group grp reads kd rows grp*8 + {0..3 lo, 4..7 hi} of
+  // a 32-row half.
+  const uint32_t wt = wave % NWT, khalf = wave / NWT;
+  const uint32_t wr = (wt / (BW / 64)) * 64, wc = (wt % (BW / 64)) * 64;
+  const uint32_t r_ = lane & 15, kq = r_ >> 2, p_ = r_ & 3, grp = lane >> 4;
+  const uint32_t krow = khalf * 32 + grp * 8 + kq;
+  const uint32_t smem0 = (uint32_t)(uintptr_t)smem;
+  uint32_t a_rd[4], b_rd[4];
+  {
+    const uint32_t fa = IA::fc(kq, grp & 1), fb = IB::fc(kq, grp & 1);
+    const uint32_t abase = smem0 + (wr / IA::PW) * 16384 + krow * IA::ROWB +
+                           p_ * 8;
+    const uint32_t bbase = smem0 + B_OFF * 2 + (wc / IB::PW) * 16384 +
+                           krow * IB::ROWB + p_ * 8;
+    const uint32_t cha = (wr % IA::PW) >> 4, chb = (wc % IB::PW) >> 4;
+#pragma unroll
+    for (uint32_t f = 0; f < 4; ++f) {
+      a_rd[f] = abase + (((cha + f) ^ fa) << 5);
+      b_rd[f] = bbase + (((chb + f) ^ fb) << 5);
+    }
+  }
+
+  f32x4 acc[4][4] = {};
+
+  // one 32-row half of a K-tile: 16 transposed reads, `mid` (the restage)
+  // while they are in flight, then 16 MFMAs in two groups
+  auto mma_half = [&](auto oa_c, auto ob_c, uint32_t cur_off, auto&& mid) {
+    constexpr uint32_t OA = decltype(oa_c)::value;
+    constexpr uint32_t OB = decltype(ob_c)::value;
+    const uint32_t a0 = a_rd[0] + cur_off, a1 = a_rd[1] + cur_off;
+    const uint32_t a2 = a_rd[2] + cur_off, a3 = a_rd[3] + cur_off;
+    const uint32_t b0 = b_rd[0] + cur_off, b1 = b_rd[1] + cur_off;
+    const uint32_t b2 = b_rd[2] + cur_off, b3 = b_rd[3] + cur_off;
+    u32x2_ al0, ah0, al1, ah1, al2, ah2, al3, ah3;
+    u32x2_ bl0, bh0, bl1, bh1, bl2, bh2, bl3, bh3;
+    asm volatile(
+        "ds_read_b64_tr_b16 %0, %12 offset:%18\n\t"
+        "ds_read_b64_tr_b16 %1, %12 offset:%19\n\t"
+        "ds_read_b64_tr_b16 %2, %13 offset:%18\n\t"
+        "ds_read_b64_tr_b16 %3, %13 offset:%19\n\t"
+        "ds_read_b64_tr_b16 %4, %14 offset:%18\n\t"
+        "ds_read_b64_tr_b16 %5, %14 offset:%19\n\t"
+        "ds_read_b64_tr_b16 %6, %15 offset:%18\n\t"
+        "ds_read_b64_tr_b16 %7, %15 offset:%19\n\t"
+        "ds_read_b64_tr_b16 %8, %16 offset:%20\n\t"
+        "ds_read_b64_tr_b16 %9, %16 offset:%21\n\t"
+        "ds_read_b64_tr_b16 %10, %17 offset:%20\n\t"
+        "ds_read_b64_tr_b16 %11, %17 offset:%21"
+        : "=&v"(al0), "=&v"(ah0), "=&v"(al1), "=&v"(ah1), "=&v"(al2),
+          "=&v"(ah2), "=&v"(al3), "=&v"(ah3), "=&v"(bl0), "=&v"(bh0),
+          "=&v"(bl1), "=&v"(bh1)
+        : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "i"(OA),
+          "i"(OA + 4 * IA::ROWB), "i"(OB), "i"(OB + 4 * IB::ROWB)
+        : "memory");
+    asm volatile(
+        "ds_read_b64_tr_b16 %0, %4 offset:%6\n\t"
+        "ds_read_b64_tr_b16 %1, %4 offset:%7\n\t"
+        "ds_read_b64_tr_b16 %2, %5 offset:%6\n\t"
+        "ds_read_b64_tr_b16 %3, %5 offset:%7"
+        : "=&v"(bl2), "=&v"(bh2), "=&v"(bl3), "=&v"(bh3)
+        : "v"(b2), "v"(b3), "i"(OB), "i"(OB + 4 * IB::ROWB)
+        : "memory");
+    mid();
+    // the waits carry the read results as in/out operands: every use of a
+    // fragment depends on the wait that retires its read
+    asm volatile("s_waitcnt lgkmcnt(4)"
+                 : "+v"(al0), "+v"(ah0), "+v"(al1), "+v"(ah1), "+v"(al2),
+                   "+v"(ah2), "+v"(al3), "+v"(ah3), "+v"(bl0), "+v"(bh0),
+                   "+v"(bl1), "+v"(bh1)
+                 :
+                 : "memory");
+    __builtin_amdgcn_sched_barrier(0);  // rule 18
+    Frag f;
+    V8 af[4], bf[4];
+    f.h[0] = al0; f.h[1] = ah0; af[0] = f.f;
+    f.h[0] = al1; f.h[1] = ah1; af[1] = f.f;
+    f.h[0] = al2; f.h[1] = ah2; af[2] = f.f;
+    f.h[0] = al3; f.h[1] = ah3; af[3] = f.f;
+    f.h[0] = bl0; f.h[1] = bh0; bf[0] = f.f;
+    f.h[0] = bl1; f.h[1] = bh1; bf[1] = f.f;
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        acc[i][j] = E8<elem_t>::mfma(af[i], bf[j], acc[i][j]);
+    __builtin_amdgcn_sched_barrier(0);  // keep the first group above the wait
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(bl2), "+v"(bh2), "+v"(bl3), "+v"(bh3)
+                 :
+                 : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    f.h[0] = bl2; f.h[1] = bh2; bf[2] = f.f;
+    f.h[0] = bl3; f.h[1] = bh3; bf[3] = f.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 2; j < 4; ++j)
+        acc[i][j] = E8<elem_t>::mfma(af[i], bf[j], acc[i][j]);
+    __builtin_amdgcn_s_setprio(0);
+  };
+  using O0 = std::integral_constant<uint32_t, 0>;
+  using OA1 = std::integral_constant<uint32_t, 32 * IA::ROWB>;
+  using OB1 = std::integral_constant<uint32_t, 32 * IB::ROWB>;
+
+  uint32_t cur = 0;  // kt % DEPTH
+  for (uint32_t kt = 0; kt < ktiles; ++kt) {
+    if (kt + 1 < ktiles)
+      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(L) : "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    const uint32_t cur_off = cur * (TILE * 2);
+    auto restage = [&] {
+      if (kt + 2 < ktiles) stage(cur == 0 ? 2 : cur - 1, kt + 2);
+    };
+    mma_half(O0{}, O0{}, cur_off, restage);
+    if constexpr (KSPLIT == 1) mma_half(OA1{}, OB1{}, cur_off, [] {});
+    cur = cur == DEPTH - 1 ? 0 : cur + 1;
+  }
+  epi.template store<4>(acc, bm + wr, bn + wc, lane);
+}
+
 // --------------------------------------------------- transpose (row-gather)
 // out[c][m] = row(m)[c]  for generic [M][C] -> [C][out_ld] bf16 transposes
 // (linear dgrad/wgrad operands, conv-wgrad dy^T and gathered im2col^T).
@@ -1923,6 +2184,45 @@ static void launch_gemm256nt(const PA& pa, const PB& pb, const EPI& epi,
     gemm256nt_kernel<PA, PB, EPI, 0>
         <<<dim3(tiles, nslices), 512, 0, cur_stream()>>>(
             pa, pb, epi, ktiles_total, tiles_n, kt_per, tiles);
+  }
+}
+
+// Streaming narrow-tile launch (gemm_nts_kernel): one block per CU, slices
+// and grouping as launch_gemm256nt. cls: 0 = 64x256, 1 = 128x256,
+// 2 = 256x128, 3 = 256x64 (M x N).
+template <int AW, int BW, class PA, class PB, class EPI>
+static void launch_gemm_nts_tile(const PA& pa, const PB& pb, const EPI& epi,
+                                 uint32_t M, uint32_t N, uint32_t K,
+                                 uint32_t splitk, bool group) {
+  uint32_t ktiles_total = ceil_div(K, 64);
+  splitk = std::max(1u, std::min(splitk, ktiles_total));
+  uint32_t kt_per = ceil_div(ktiles_total, splitk);
+  uint32_t nslices = ceil_div(ktiles_total, kt_per);
+  uint32_t tiles_n = ceil_div(N, BW);
+  uint32_t tiles = ceil_div(M, AW) * tiles_n;
+  if (group) {
+    gemm_nts_kernel<AW, BW, PA, PB, EPI, 1>
+        <<<8 * tiles * ceil_div(nslices, 8u), 512, 0, cur_stream()>>>(
+            pa, pb, epi, ktiles_total, tiles_n, kt_per, tiles);
+  } else {
+    TORCH_CHECK(nslices <= 65535, "gemm_nts: split-K ", nslices,
+                " exceeds the grid's y extent");
+    gemm_nts_kernel<AW, BW, PA, PB, EPI, 0>
+        <<<dim3(tiles, nslices), 512, 0, cur_stream()>>>(
+            pa, pb, epi, ktiles_total, tiles_n, kt_per, tiles);
+  }
+}
+
+template <class PA, class PB, class EPI>
+static void launch_gemm_nts(int cls, const PA& pa, const PB& pb,
+                            const EPI& epi, uint32_t M, uint32_t N, uint32_t K,
+                            uint32_t splitk, bool group) {
+  switch (cls) {
+    case 0: launch_gemm_nts_tile<64, 256>(pa, pb, epi, M, N, K, splitk, group); break;
+    case 1: launch_gemm_nts_tile<128, 256>(pa, pb, epi, M, N, K, splitk, group); break;
+    case 2: launch_gemm_nts_tile<256, 128>(pa, pb, epi, M, N, K, splitk, group); break;
+    case 3: launch_gemm_nts_tile<256, 64>(pa, pb, epi, M, N, K, splitk, group); break;
+    default: TORCH_CHECK(false, "gemm_nts: no narrow tile class ", cls);
   }
 }
 
@@ -2497,6 +2797,71 @@ std::tuple<bool, long, bool> wgrad_nt256_plan(long Ko, long RSC, long NPQ) {
   return {use, (long)splitk, group};
 }
 
+// tile class of the streaming narrow-tile kernel (gemm_nts_kernel) that
+// covers a (Ko, RSC) wgrad: 0 = 64x256 (Ko <= 64), 1 = 128x256 (Ko <= 128),
+// 3 = 256x64 (RSC <= 64), 2 = 256x128 (RSC <= 128), -1 = none
+static int wgrad_narrow_class(long Ko, long RSC) {
+  if (Ko <= 64) return 0;
+  if (Ko <= 128) return 1;
+  if (RSC <= 64) return 3;
+  if (RSC <= 128) return 2;
+  return -1;
+}
+
+// the shape classes on which the narrow-tile kernel won every round of the
+// per-shape A/B (profiles/resnet50_mi355x.md; bs4096: x1.04 on (64, 256),
+// x1.18-1.44 on the other seven); the others keep gemm_nt_kernel. Only full
+// narrow sides and the measured range of the wide side are claimed.
+// (Ko, RSC) = (64, 64) lost (x0.79: three quarters of the 256 columns are
+// padding, and the 128x64 tile is already at 5.85 TB/s).
+static bool wgrad_narrow_routed(int cls, long Ko, long RSC) {
+  switch (cls) {
+    case 0: return Ko == 64 && RSC >= 256;
+    case 1: return Ko == 128 && RSC >= 256;
+    case 2: return RSC == 128 && Ko >= 256;
+    case 3: return RSC == 64 && Ko >= 256;
+  }
+  return false;
+}
+
+static const char* const kNarrowTileNames[4] ={"64x256", "128x256", "256x128",
+                                                "256x64"};
+
+// routing plan of the narrow-tile kernel for a (Ko, RSC, NPQ) wgrad: (use it,
+// tile class or "" when no class covers the shape, split-K, XCD-grouped
+// launch). Gate and settings are measured per shape class
+// (tools/bench_wgrad.py --narrow, profiles/resnet50_mi355x.md).
+std::tuple<bool, std::string, long, bool> wgrad_narrow_plan(long Ko, long RSC,
+                                                            long NPQ) {
+  const int cls = wgrad_narrow_class(Ko, RSC);
+  if (cls < 0) return {false, "", 1, false};
+  static const uint32_t tw[4][2] = {{64, 256}, {128, 256}, {256, 128}, {256, 64}};
+  uint32_t ktiles = ceil_div((uint32_t)NPQ, 64);
+  uint32_t tiles =
+      ceil_div((uint32_t)Ko, tw[cls][0]) * ceil_div((uint32_t)RSC, tw[cls][1]);
+  // the K-tile floor of the 256² kernel, for the same reason: only the
+  // bs4096 regime was measured. DTMX_NARROW_MIN_KTILES overrides it.
+  static const uint32_t min_ktiles = [] {
+    const char* v = getenv("DTMX_NARROW_MIN_KTILES");
+    return v ? (uint32_t)atoi(v) : 2048u;
+  }();
+  // One block per CU: 256 blocks. 128 blocks lost 5-35 % everywhere, 512
+  // were within 2 % of 256. The XCD-grouped launch (slices a multiple of 8)
+  // gained 6 % / 4-7 % on the 128x256 class at 2 / 5 tiles and was within
+  // noise (+-1 %) elsewhere, so only that class groups.
+  bool group = cls == 1 && tiles > 1 && tiles <= 32;
+  uint32_t splitk = std::max(1u, std::min(ktiles, 256u / tiles));
+  if (group) {
+    splitk = std::max(8u, splitk / 8 * 8);
+    if (splitk > ktiles) {  // cannot give every die a slice: do not group
+      group = false;
+      splitk = ktiles;
+    }
+  }
+  bool use = ktiles >= min_ktiles && wgrad_narrow_routed(cls, Ko, RSC);
+  return {use, kNarrowTileNames[cls], (long)splitk, group};
+}
+
 // split-K that conv_wgrad hands to launch_gemm_nt when the 256² kernel is
 // not used (host-only; shared with the read-only wgrad_nt_plan binding)
 static uint32_t wgrad_nt_splitk_of(uint32_t Ko, uint32_t RSC, uint32_t NPQ) {
@@ -2530,12 +2895,14 @@ std::tuple<long, long, long, bool, long, long> wgrad_nt_plan(long Ko, long RSC,
 }
 
 // transpose-free wgrad: dy and the im2col view of x are read NHWC-native by
-// the contraction-major (NT) kernels. use256 selects gemm256nt_kernel with
-// the given split-K / grouping; otherwise launch_gemm_nt routes as before.
+// the contraction-major (NT) kernels. kern = kNt256 selects gemm256nt_kernel,
+// kNtNarrow gemm_nts_kernel (tile class from the shape), each with the given
+// split-K / grouping; kNtOld lets launch_gemm_nt route as before.
+enum { kNtOld = 0, kNt256 = 1, kNtNarrow = 2 };
 template <typename elem_t>
 static at::Tensor wgrad_nt_run(const at::Tensor& x, const at::Tensor& dy,
                                long R, long S, long stride, long ph, long pw,
-                               bool use256, uint32_t splitk, bool group,
+                               int kern, uint32_t splitk, bool group,
                                bool want_f32 = false) {
   uint32_t N = x.size(0), C = x.size(1), H = x.size(2), W_ = x.size(3);
   uint32_t Ko = dy.size(1), P = dy.size(2), Q = dy.size(3);
@@ -2557,8 +2924,11 @@ static at::Tensor wgrad_nt_run(const at::Tensor& x, const at::Tensor& dy,
   pb.u = stride; pb.v = stride; pb.ph = ph; pb.pw = pw;
   pb.dQ.init(Q); pb.dPQ.init(P * Q); pb.dC.init(C); pb.dS.init(S);
   EpiAtomicF32<elem_t> epi{dw32.data_ptr<float>(), Ko, RSC};
-  if (use256)
+  if (kern == kNt256)
     launch_gemm256nt(pa, pb, epi, Ko, RSC, M, splitk, group);
+  else if (kern == kNtNarrow)
+    launch_gemm_nts(wgrad_narrow_class(Ko, RSC), pa, pb, epi, Ko, RSC, M,
+                    splitk, group);
   else
     launch_gemm_nt(pa, pb, epi, Ko, RSC, M, splitk);
   if (want_f32) {  // the fp32 sums before the 16-bit rounding (tests)
@@ -2581,49 +2951,89 @@ static at::Tensor wgrad_nt_run(const at::Tensor& x, const at::Tensor& dy,
   return dwm.permute({0, 3, 1, 2});  // logical (K,C,R,S), channels_last
 }
 
-// test/bench entry: always gemm256nt_kernel, explicit split-K and grouping
-at::Tensor conv_wgrad_nt256(const at::Tensor& x, const at::Tensor& dy, long R,
-                            long S, long stride, long pad, long splitk,
-                            bool group) {
+// envelope of the explicit-settings entries of the Col/Row-context kernels
+// (conv_wgrad_nt256, conv_wgrad_narrow): raises with the violated condition
+static void wgrad_nt_envelope(const char* op, const at::Tensor& x,
+                              const at::Tensor& dy, long R, long S,
+                              long stride, long pad, long splitk) {
   TORCH_CHECK(x.is_cuda() && dy.is_cuda(),
-              "conv_wgrad_nt256: x and dy must be CUDA tensors");
+              op, ": x and dy must be CUDA tensors");
   TORCH_CHECK((x.scalar_type() == at::kBFloat16 ||
                x.scalar_type() == at::kHalf) &&
                   dy.scalar_type() == x.scalar_type(),
-              "conv_wgrad_nt256: x and dy must share a 16-bit dtype "
+              op, ": x and dy must share a 16-bit dtype "
               "(bfloat16/float16)");
   TORCH_CHECK(x.dim() == 4 && dy.dim() == 4 &&
                   x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
                   dy.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_wgrad_nt256: x and dy must be NHWC (channels_last) "
+              op, ": x and dy must be NHWC (channels_last) "
               "4-d tensors");
   TORCH_CHECK(R >= 1 && S >= 1 && stride >= 1 && pad >= 0,
-              "conv_wgrad_nt256: bad window (R, S, stride >= 1, pad >= 0)");
+              op, ": bad window (R, S, stride >= 1, pad >= 0)");
   const long N = x.size(0), C = x.size(1), H = x.size(2), W_ = x.size(3);
   const long Ko = dy.size(1), P = dy.size(2), Q = dy.size(3);
   TORCH_CHECK(dy.size(0) == N && P == (H + 2 * pad - R) / stride + 1 &&
                   Q == (W_ + 2 * pad - S) / stride + 1,
-              "conv_wgrad_nt256: dy shape does not match x and the window");
-  TORCH_CHECK(C % 8 == 0, "conv_wgrad_nt256: C % 8 == 0 required, got C = ", C);
+              op, ": dy shape does not match x and the window");
+  TORCH_CHECK(C % 8 == 0, op, ": C % 8 == 0 required, got C = ", C);
   TORCH_CHECK(Ko % 8 == 0,
-              "conv_wgrad_nt256: Ko % 8 == 0 required, got Ko = ", Ko);
+              op, ": Ko % 8 == 0 required, got Ko = ", Ko);
   TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
                   (uintptr_t)dy.data_ptr() % 16 == 0,
-              "conv_wgrad_nt256: x and dy must be 16-byte aligned");
+              op, ": x and dy must be 16-byte aligned");
   const long NPQ = N * P * Q;
   TORCH_CHECK(NPQ > 0 && NPQ < (1L << 32),
-              "conv_wgrad_nt256: N*P*Q < 2^32 required, got ", NPQ);
+              op, ": N*P*Q < 2^32 required, got ", NPQ);
   TORCH_CHECK(H * W_ * C < (1L << 31) && R * S * C < (1L << 31),
-              "conv_wgrad_nt256: H*W*C and R*S*C must be < 2^31");
+              op, ": H*W*C and R*S*C must be < 2^31");
   const long ktiles = (NPQ + 63) / 64;
   TORCH_CHECK(splitk >= 1 && splitk <= ktiles,
-              "conv_wgrad_nt256: 1 <= splitk <= ceil(N*P*Q / 64) required, "
+              op, ": 1 <= splitk <= ceil(N*P*Q / 64) required, "
               "got splitk = ", splitk, " with ", ktiles, " K-tiles");
+}
+
+// test/bench entry: always gemm256nt_kernel, explicit split-K and grouping
+at::Tensor conv_wgrad_nt256(const at::Tensor& x, const at::Tensor& dy, long R,
+                            long S, long stride, long pad, long splitk,
+                            bool group) {
+  wgrad_nt_envelope("conv_wgrad_nt256", x, dy, R, S, stride, pad, splitk);
   DTMX_DISPATCH_16(x.scalar_type(), "conv_wgrad_nt256", {
-    return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, pad, true,
+    return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, pad, kNt256,
                                 (uint32_t)splitk, group);
   });
   return at::Tensor();
+}
+
+// test/bench entry: always gemm_nts_kernel on the tile class that covers the
+// shape, explicit split-K and grouping; want_f32 returns the fp32 split-K
+// sums [Ko][R*S*C] before the 16-bit rounding
+static at::Tensor conv_wgrad_narrow_impl(const char* op, const at::Tensor& x,
+                                         const at::Tensor& dy, long R, long S,
+                                         long stride, long pad, long splitk,
+                                         bool group, bool want_f32) {
+  wgrad_nt_envelope(op, x, dy, R, S, stride, pad, splitk);
+  TORCH_CHECK(wgrad_narrow_class(dy.size(1), R * S * x.size(1)) >= 0, op,
+              ": Ko <= 128 or R*S*C <= 128 required, got Ko = ", dy.size(1),
+              ", R*S*C = ", R * S * x.size(1));
+  DTMX_DISPATCH_16(x.scalar_type(), op, {
+    return wgrad_nt_run<elem_t>(x, dy, R, S, stride, pad, pad, kNtNarrow,
+                                (uint32_t)splitk, group, want_f32);
+  });
+  return at::Tensor();
+}
+
+at::Tensor conv_wgrad_narrow(const at::Tensor& x, const at::Tensor& dy, long R,
+                             long S, long stride, long pad, long splitk,
+                             bool group) {
+  return conv_wgrad_narrow_impl("conv_wgrad_narrow", x, dy, R, S, stride, pad,
+                                splitk, group, false);
+}
+
+at::Tensor conv_wgrad_narrow_acc32(const at::Tensor& x, const at::Tensor& dy,
+                                   long R, long S, long stride, long pad,
+                                   long splitk, bool group) {
+  return conv_wgrad_narrow_impl("conv_wgrad_narrow_acc32", x, dy, R, S, stride,
+                                pad, splitk, group, true);
 }
 
 // test entry: the fp32 split-K sums [Ko][R*S*C] before the 16-bit rounding,
@@ -2683,6 +3093,19 @@ static at::Tensor conv_wgrad_impl(const at::Tensor& x, const at::Tensor& dy,
           return wgrad_nt_run<elem_t>(x, dy, R, S, stride, ph, pw, true,
                                       (uint32_t)std::get<1>(plan),
                                       std::get<2>(plan));
+      }
+      // DTMX_DISABLE_NARROW=1: the routing without the narrow-tile kernel
+      static const bool no_narrow = env_flag("DTMX_DISABLE_NARROW");
+      if (!no_narrow) {
+        auto plan = wgrad_narrow_plan(Ko, RSC, M);
+        const bool envelope =
+            (uint64_t)H * W_ * C < (1ull << 31) &&
+            (uintptr_t)x.data_ptr() % 16 == 0 &&
+            (uintptr_t)dy.data_ptr() % 16 == 0;
+        if (std::get<0>(plan) && envelope)
+          return wgrad_nt_run<elem_t>(x, dy, R, S, stride, ph, pw, kNtNarrow,
+                                      (uint32_t)std::get<2>(plan),
+                                      std::get<3>(plan));
       }
       const uint32_t splitk = wgrad_nt_splitk_of(Ko, RSC, M);
       return wgrad_nt_run<elem_t>(x, dy, R, S, stride, ph, pw, false, splitk,

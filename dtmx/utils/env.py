@@ -46,6 +46,9 @@ see profiles/resnet50_mi355x.md for the numbers behind each):
   DTMX_BN_COL           0 = strided-chunk BN elementwise kernels (no
                         fixed-column register-resident tables)
   DTMX_DISABLE_GEMM256  1 = never route to the 256^2 8-phase GEMM
+  DTMX_DISABLE_NARROW   1 = never route wgrad to the streaming narrow-tile
+                        kernel (the stem / layer1 / layer2 routing before it)
+  DTMX_NARROW_MIN_KTILES  K-tile floor of that routing (default 2048)
   DTMX_NT_GROUP         0/1 = force XCD-grouped wgrad split-K off/on
                         (default: auto, only the tile class that wins)
   DTMX_WGRAD_TARGET_BLOCKS   wgrad split-K grid target (default 512)

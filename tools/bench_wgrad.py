@@ -123,6 +123,81 @@ def nt256(bs, new, sweep, rounds=3):
         del x, dy
 
 
+# The ResNet-50 wgrad shape classes that the 256x256 kernel does not take:
+# the stem (C padded to 8), layer1 and layer2 except the layer2 downsample.
+# (name, convs per step, C_in, K_out, H_in, R, stride, pad)
+NARROW_SHAPES = [
+    ("l1.0.c1 1x1", 1, 64, 64, 56, 1, 1, 0),
+    ("l1.x.c1 1x1", 2, 256, 64, 56, 1, 1, 0),
+    ("l1.x.c2 3x3", 3, 64, 64, 56, 3, 1, 1),
+    ("stem    7x7s2", 1, 8, 64, 224, 7, 2, 3),
+    ("l1.x.c3 1x1", 4, 64, 256, 56, 1, 1, 0),
+    ("l2.0.c1 1x1", 1, 256, 128, 56, 1, 1, 0),
+    ("l2.x.c1 1x1", 3, 512, 128, 28, 1, 1, 0),
+    ("l2.x.c2 3x3", 4, 128, 128, 28, 3, 1, 1),
+    ("l2.x.c3 1x1", 4, 128, 512, 28, 1, 1, 0),
+]
+_NARROW_TILE = {"64x256": (64, 256), "128x256": (128, 256),
+                "256x128": (256, 128), "256x64": (256, 64)}
+
+
+def narrow(bs, new, sweep, rounds=3):
+    """Per-shape old-vs-new wgrad in ONE process, alternating, median of
+    `rounds`. ext.conv_wgrad runs the old routing (the caller set
+    DTMX_DISABLE_NARROW=1 before the extension's first call); the streaming
+    narrow-tile kernel runs through ext.conv_wgrad_narrow with the planned
+    split-K / grouping (ext.wgrad_narrow_plan) and, with sweep, at 128 / 256 /
+    512 blocks with and without XCD grouping. Floor = max(bytes / 6 TB/s,
+    flops / 900 TF) with bytes = dy once + x once; the TB/s column is those
+    bytes over the measured time. wins = rounds in which new beat old."""
+    torch.manual_seed(0)
+    tot_old = tot_floor = 0.0
+    for (name, convs, C, Ko, H, R, st, pa) in NARROW_SHAPES:
+        P = (H + 2 * pa - R) // st + 1
+        x = torch.randn(bs, C, H, H, dtype=torch.bfloat16, device=DEV).contiguous(
+            memory_format=torch.channels_last)
+        dy = torch.randn(bs, Ko, P, P, dtype=torch.bfloat16, device=DEV).contiguous(
+            memory_format=torch.channels_last)
+        npq, rsc = bs * P * P, R * R * C
+        fl = 2.0 * npq * Ko * rsc
+        gb = (dy.numel() + x.numel()) * 2 / 1e9
+        floor = max(gb / 6e3, fl / 900e12)
+        ktiles = _cdiv(npq, 64)
+        use, cls, sk, grp = ext.wgrad_narrow_plan(Ko, rsc, npq)
+        tm, tn = _NARROW_TILE[cls]
+        tiles = _cdiv(Ko, tm) * _cdiv(rsc, tn)
+        cfgs = [("plan", sk, grp)] if new else []
+        if new and sweep:
+            for tgt in (128, 256, 512):
+                k = max(1, min(ktiles, tgt // tiles))
+                cfgs.append((f"t{tgt}", k, False))
+                k8 = max(8, (k // 8) * 8)  # grouped: slices a multiple of 8
+                cfgs.append((f"t{tgt}g", min(ktiles, k8), True))
+        res = {"old": []}
+        for _ in range(rounds):
+            res["old"].append(timeit(lambda: ext.conv_wgrad(x, dy, R, R, st, pa)))
+            for (cn, k, g) in cfgs:
+                res.setdefault((cn, k, g), []).append(timeit(
+                    lambda: ext.conv_wgrad_narrow(x, dy, R, R, st, pa, k, g)))
+        so = sorted(res["old"])[len(res["old"]) // 2]
+        tot_old += convs * so
+        tot_floor += convs * floor
+        print(f"{name} x{convs} bs{bs} {C}->{Ko} {H}^2 tile={cls} tiles={tiles} "
+              f"routed={int(use)}: old {so*1e3:7.3f} ms {fl/so/1e12:6.1f} TF "
+              f"{gb/so/1e3:5.2f} TB/s  floor {floor*1e3:6.3f} ms", flush=True)
+        for key, v in res.items():
+            if key == "old":
+                continue
+            s = sorted(v)[len(v) // 2]
+            wins = sum(n < o for n, o in zip(v, res["old"]))
+            print(f"    narrow {key[0]:6s} splitk={key[1]:4d} group={int(key[2])}: "
+                  f"{s*1e3:7.3f} ms {fl/s/1e12:6.1f} TF {gb/s/1e3:5.2f} TB/s  "
+                  f"x{so/s:5.3f} vs old  wins {wins}/{rounds}", flush=True)
+        del x, dy
+    print(f"sum over the step's {sum(s[1] for s in NARROW_SHAPES)} convs: old "
+          f"{tot_old*1e3:.2f} ms, floor {tot_floor*1e3:.2f} ms", flush=True)
+
+
 def triad():
     """bf16 RW-mix ceilings for the BN elementwise kernels: what does THIS
     box sustain on d=a+b (2R+1W, the bn_bwd_dx mix) and b=a*s (1R+1W, the
@@ -147,12 +222,20 @@ if __name__ == "__main__":
                     help="layer3/4 + downsample shapes: 0 = old routing only, "
                          "1 = old and the 256^2 kernel alternating")
     ap.add_argument("--sweep", action="store_true",
-                    help="with --nt256 1: also sweep split-K targets "
+                    help="with --nt256 1 / --narrow 1: also sweep split-K targets "
                          "128/256/512 with and without XCD grouping")
     ap.add_argument("--bs", type=int, default=4096,
                     help="per-GPU batch for --nt256 (flagship: 4096)")
+    ap.add_argument("--narrow", type=int, choices=[0, 1], default=None,
+                    help="stem / layer1 / layer2 shape classes: 0 = old routing "
+                         "only, 1 = old and the narrow-tile kernel alternating "
+                         "(--sweep: also 128/256/512 blocks, grouped or not)")
     args = ap.parse_args()
-    if args.nt256 is not None:
+    if args.narrow is not None:
+        # conv_wgrad reads the flag once, at its first call
+        os.environ["DTMX_DISABLE_NARROW"] = "1"
+        narrow(args.bs, bool(args.narrow), args.sweep)
+    elif args.nt256 is not None:
         # conv_wgrad reads the flag once, at its first call
         os.environ["DTMX_DISABLE_NT256"] = "1"
         nt256(args.bs, bool(args.nt256), args.sweep)
