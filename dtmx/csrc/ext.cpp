@@ -47,6 +47,11 @@ at::Tensor gconv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, b
 // lineconv.hip
 at::Tensor lineconv_fwd(const at::Tensor&, const at::Tensor&);
 at::Tensor lineconv_dgrad(const at::Tensor&, const at::Tensor&);
+// stemconv.hip
+std::vector<at::Tensor> stemconv_fwd(const at::Tensor&, const at::Tensor&, long, long,
+                                     long, bool);
+at::Tensor stemconv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, long,
+                          long, bool, long);
 // avgpool.hip
 at::Tensor avgpool_fwd(const at::Tensor&, long, long, long, bool);
 at::Tensor avgpool_bwd(const at::Tensor&, long, long, long, long, long, bool);
@@ -173,6 +178,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // the (Ko,C,1,T) or (Ko,C,T,1) channels_last parameter
   m.def("lineconv_fwd", &dtmx::lineconv_fwd, py::arg("x"), py::arg("w"));
   m.def("lineconv_dgrad", &dtmx::lineconv_dgrad, py::arg("dy"), py::arg("w"));
+  // First layer, 1 <= C <= 4 input channels read as stored (no padded copy):
+  // R <= 7, S <= 8, stride 1|2, pad_h < R, pad_w < S, Ko % 8 == 0; w is the
+  // (Ko,C,R,S) parameter in either dense layout. fwd -> [y, psum, psumsq]
+  // (fp32 [tiles][Ko] slabs of the rounded y, empty without want_stats);
+  // wgrad returns dw in the layout w_channels_last names, slices = 0: auto.
+  m.def("stemconv_fwd", &dtmx::stemconv_fwd, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("pad_h"), py::arg("pad_w"),
+        py::arg("want_stats") = false);
+  m.def("stemconv_wgrad", &dtmx::stemconv_wgrad, py::arg("x"), py::arg("dy"),
+        py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad_h"),
+        py::arg("pad_w"), py::arg("w_channels_last"), py::arg("slices") = 0);
   // test/bench entry: always the 256² contraction-major kernel
   m.def("conv_wgrad_nt256", &dtmx::conv_wgrad_nt256, py::arg("x"),
         py::arg("dy"), py::arg("R"), py::arg("S"), py::arg("stride"),

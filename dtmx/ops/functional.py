@@ -8,6 +8,7 @@ Compute dtype bf16 (fp32 accumulate inside kernels); CPU path is fp32 torch.
 Reference kernel parity:
   conv fwd/dgrad/wgrad   <- src/operator/nn/convolution.cu (cuDNN/im2col)
   1xT / Tx1 line conv    <- src/operator/nn/convolution.cu (kernel=(1,7), ...)
+  first-layer conv       <- src/operator/nn/convolution.cu (3-channel data)
   depthwise 3x3 conv     <- src/operator/nn/depthwise_convolution_tf.cuh
   grouped 3x3 conv       <- src/operator/nn/convolution.cu (num_group > 1)
   batch_norm fwd/bwd     <- src/operator/nn/batch_norm.cu:208-360
@@ -160,10 +161,120 @@ def _lineconv_routed(x, w, stride, ph, pw) -> bool:
     return w.shape[3] != 1 or (w.shape[2] - 1) * x.shape[3] <= 32
 
 
+class _StemConvNHWC(torch.autograd.Function):
+    """First-layer conv, 1..4 input channels, on the stemconv.hip kernels. `w`
+    is the parameter as stored, logical (Ko,C,R,S) in either dense layout; dw
+    comes back in the same layout, from stemconv_wgrad on x as stored.
+    native_fwd: stemconv_fwd (x as stored, fused BN statistics); otherwise the
+    forward zero-pads x and w to 8 channels for the generic kernels, as the
+    parent path does, but keeps only the unpadded x for backward. There is no
+    stem dgrad kernel (the image needs no gradient in training): dx, when
+    asked for, pads w to 8 channels, runs the generic dgrad and slices."""
+
+    @staticmethod
+    def forward(ctx, x, w, stride, ph, pw, want_stats, native_fwd):
+        ext = require_ext()
+        ctx.save_for_backward(x, w)
+        ctx.conv = (stride, ph, pw)
+        if native_fwd:
+            y, ps, pss = ext.stemconv_fwd(x, w, stride, ph, pw, want_stats)
+        else:
+            padc = (0, 0, 0, 0, 0, 8 - x.shape[1])
+            x8 = F.pad(x, padc).contiguous(memory_format=torch.channels_last)
+            w8 = F.pad(w, padc).contiguous(memory_format=torch.channels_last)
+            ps = pss = y = None
+            if w.shape[2] != w.shape[3] or ph != pw:
+                y = ext.conv_fwd_hw(x8, w8, stride, ph, pw)
+            elif want_stats:
+                y, ps, pss = ext.conv_fwd_stats(x8, w8, stride, ph)
+            else:
+                y = ext.conv_fwd(x8, w8, stride, ph)
+            if ps is None:
+                ps = pss = y.new_zeros(0, dtype=torch.float32)
+        ctx.mark_non_differentiable(ps, pss)
+        return y, ps, pss
+
+    @staticmethod
+    def backward(ctx, dy, _dps=None, _dpss=None):
+        ext = require_ext()
+        x, w = ctx.saved_tensors
+        stride, ph, pw = ctx.conv
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        if dy.data_ptr() % 16:
+            dy = dy.clone(memory_format=torch.channels_last)
+        C, (R, S) = x.shape[1], w.shape[2:]
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            w8 = F.pad(w, (0, 0, 0, 0, 0, 8 - C)).contiguous(
+                memory_format=torch.channels_last)
+            if R == S and ph == pw:
+                dx = ext.conv_dgrad(dy, w8, stride, ph, x.shape[2], x.shape[3])
+            else:
+                dx = ext.conv_dgrad_hw(dy, w8, stride, ph, pw, x.shape[2], x.shape[3])
+            dx = dx[:, :C].contiguous(memory_format=torch.channels_last)
+        if ctx.needs_input_grad[1]:
+            dw = ext.stemconv_wgrad(x, dy, R, S, stride, ph, pw,
+                                    not w.is_contiguous())
+        return dx, dw, None, None, None, None, None
+
+
+def _stemconv_in_envelope(x, w, stride, ph, pw) -> bool:
+    """The cases stemconv.hip implements: GPU bf16/fp16, 1 <= C <= 4,
+    Ko % 8 == 0, R <= 7, S <= 8, stride 1|2, ph < R, pw < S, a non-empty output,
+    fewer than 2^31 elements of x and pixels of y (offsets are 64-bit: the
+    bs4096 ResNet stem writes 3.3e9 elements) and a dense weight in either
+    layout. x and w need element alignment only."""
+    if x.dim() != 4 or w.dim() != 4 or not isinstance(stride, int):
+        return False
+    Ko, C, R, S = w.shape
+    N, Cx, H, W = x.shape
+    if not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16)
+            and w.dtype == x.dtype and w.device == x.device
+            and Cx == C and 1 <= C <= 4 and Ko > 0 and Ko % 8 == 0
+            and 1 <= R <= 7 and 1 <= S <= 8 and stride in (1, 2)
+            and 0 <= ph < R and 0 <= pw < S
+            and N > 0 and H + 2 * ph >= R and W + 2 * pw >= S):
+        return False
+    P, Q = (H + 2 * ph - R) // stride + 1, (W + 2 * pw - S) // stride + 1
+    return (x.numel() < 2 ** 31 and N * P * Q < 2 ** 31
+            and (w.is_contiguous()
+                 or w.is_contiguous(memory_format=torch.channels_last)))
+
+
+def _stemconv_routed(x, w, stride, ph, pw) -> bool:
+    """In the envelope and in a shape class where a stem kernel measured
+    faster than the zero-padded 8-channel path (tools/bench_stemconv.py,
+    profiles/resnet50_mi355x.md): stemconv_wgrad won every measured stem
+    (1.5-2.2x), so the whole envelope takes _StemConvNHWC."""
+    return _stemconv_in_envelope(x, w, stride, ph, pw)
+
+
+def _stemconv_fwd_routed(x, w, stride, ph, pw) -> bool:
+    """stemconv_fwd lost every measured stem (0.38-0.66x of the padded path,
+    its F.pad passes included), so no class is routed to it; the entry point
+    still accepts the envelope."""
+    return False
+
+
+def _conv2d_dispatch(x, w, stride, padding) -> str:
+    """The path DF.conv2d takes for these operands: "stemconv"
+    (_StemConvNHWC), "hip" (the dense / gather / per-axis / line kernels on
+    8-channel-padded operands) or "torch"."""
+    if not _use_hip(x, op="conv"):
+        return "torch"
+    ph, pw = (padding, padding) if isinstance(padding, int) else padding
+    if "stemconv" not in _FALLBACK and _stemconv_routed(x, w, stride, int(ph), int(pw)):
+        return "stemconv"
+    return "hip"
+
+
 def conv2d(x, w, stride: int = 1, padding=0, want_stats: bool = False):
     """padding: an int, or an (h, w) pair; the kernel shape is read from w.
 
-    A square call with int padding takes the dense / gather kernels with
+    A first-layer call (1..4 input channels, _stemconv_routed) takes the stem
+    wgrad kernel, which reads x as stored; its forward stays on the zero-padded
+    8-channel kernels where stemconv_fwd measured slower (_stemconv_fwd_routed).
+    DTMX_FALLBACK=stemconv restores the zero-padded path below for both. A square call with int padding takes the dense / gather kernels with
     their fused epilogues. 1xT / Tx1 same-padded stride-1 calls take the line
     kernels where those measured faster (_lineconv_routed; DTMX_FALLBACK=
     lineconv: the generic per-axis path); every other rectangular or per-axis
@@ -176,6 +287,12 @@ def conv2d(x, w, stride: int = 1, padding=0, want_stats: bool = False):
     if not isinstance(padding, int):
         ph, pw = (int(p) for p in padding)
         padding = ph if ph == pw and w.shape[2] == w.shape[3] else (ph, pw)
+    if _conv2d_dispatch(x, w, stride, padding) == "stemconv":
+        ph, pw = (padding, padding) if isinstance(padding, int) else padding
+        x = x.contiguous(memory_format=torch.channels_last)
+        y, ps, pss = _StemConvNHWC.apply(x, w, stride, ph, pw, want_stats,
+                                         _stemconv_fwd_routed(x, w, stride, ph, pw))
+        return (y, ps, pss) if want_stats else y
     if _use_hip(x, op="conv") and not isinstance(padding, int):
         C = x.shape[1]
         if C % 8 != 0:
