@@ -37,10 +37,14 @@ std::vector<at::Tensor> conv_dgrad_bnfuse(const at::Tensor&, const at::Tensor&,
 std::vector<std::tuple<long, long, double>> wgrad_ws_stats();
 // dwconv.hip
 at::Tensor dwconv_fwd(const at::Tensor&, const at::Tensor&, long, long);
+std::vector<at::Tensor> dwconv_fwd_stats(const at::Tensor&, const at::Tensor&, long,
+                                         long);
 at::Tensor dwconv_dgrad(const at::Tensor&, const at::Tensor&, long, long, long, long);
 at::Tensor dwconv_wgrad(const at::Tensor&, const at::Tensor&, long, long);
 // gconv.hip
 at::Tensor gconv_fwd(const at::Tensor&, const at::Tensor&, long, long, long);
+std::vector<at::Tensor> gconv_fwd_stats(const at::Tensor&, const at::Tensor&, long, long,
+                                        long);
 at::Tensor gconv_dgrad(const at::Tensor&, const at::Tensor&, long, long, long, long,
                        long);
 at::Tensor gconv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, bool);
@@ -227,11 +231,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("NPQ"));
   m.def("dwconv_fwd", &dtmx::dwconv_fwd, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("pad"));
+  // returns (y, psum, psumsq): y and the fused BN statistic slabs of the
+  // rounded y, fp32 [blocks][C]
+  m.def("dwconv_fwd_stats", &dtmx::dwconv_fwd_stats, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("pad"));
   m.def("dwconv_dgrad", &dtmx::dwconv_dgrad, py::arg("dy"), py::arg("w"),
         py::arg("stride"), py::arg("pad"), py::arg("H"), py::arg("W"));
   m.def("dwconv_wgrad", &dtmx::dwconv_wgrad, py::arg("x"), py::arg("dy"),
         py::arg("stride"), py::arg("pad"));
   m.def("gconv_fwd", &dtmx::gconv_fwd, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("pad"), py::arg("groups"));
+  // returns (y, psum, psumsq), slabs fp32 [pixel walkers][C]
+  m.def("gconv_fwd_stats", &dtmx::gconv_fwd_stats, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("pad"), py::arg("groups"));
   m.def("gconv_dgrad", &dtmx::gconv_dgrad, py::arg("dy"), py::arg("w"),
         py::arg("stride"), py::arg("pad"), py::arg("groups"), py::arg("H"),

@@ -340,15 +340,19 @@ class _DepthwiseConvNHWC(torch.autograd.Function):
     `w` is the parameter as stored, logical (C,1,3,3) = memory [C][3][3]."""
 
     @staticmethod
-    def forward(ctx, x, w, stride, padding):
+    def forward(ctx, x, w, stride, padding, want_stats=False):
         ext = require_ext()
         ctx.save_for_backward(x, w)
         ctx.stride = stride
         ctx.padding = padding
-        return ext.dwconv_fwd(x, w, stride, padding)
+        if not want_stats:
+            return ext.dwconv_fwd(x, w, stride, padding)
+        y, ps, pss = ext.dwconv_fwd_stats(x, w, stride, padding)
+        ctx.mark_non_differentiable(ps, pss)
+        return y, ps, pss
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, _dps=None, _dpss=None):
         ext = require_ext()
         x, w = ctx.saved_tensors
         dy = dy.contiguous(memory_format=torch.channels_last)
@@ -358,7 +362,7 @@ class _DepthwiseConvNHWC(torch.autograd.Function):
                                   x.shape[2], x.shape[3])
         if ctx.needs_input_grad[1]:
             dw = ext.dwconv_wgrad(x, dy, ctx.stride, ctx.padding)
-        return dx, dw, None, None
+        return dx, dw, None, None, None
 
 
 def _dwconv_in_envelope(x, w, stride, padding) -> bool:
@@ -375,16 +379,46 @@ def _dwconv_in_envelope(x, w, stride, padding) -> bool:
             and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
 
 
-def depthwise_conv2d(x, w, stride: int = 1, padding: int = 0):
+def _dwconv_stats_routed(x, w, stride, padding) -> bool:
+    """Shape classes where dwconv_fwd_stats plus the slab reduce measured
+    faster than dwconv_fwd plus the BatchNorm's own statistics pass by more
+    than the run-to-run spread (tools/bench_dwconv.py --stats, profiles/
+    mobilenet_mi355x.md; bf16, batch 256 and 32). At batch 256 every layer
+    with a 28x28 or larger output won 6-33 % (all have >= 25.7 M output
+    elements); with a 14x14 or 7x7 output one layer won 10 % and the other
+    eight lost 2-22 %. At batch 32 (<= 14.4 M elements) the 28x28-and-larger
+    layers lost 3-22 % but for the two 144-channel ones, and the small ones
+    were within their 20-50 % spread. So: an output of at least 28x28 and at
+    least 25 M elements. Between 14.4 M and 25.7 M nothing is measured; it
+    stays on the BatchNorm's own pass."""
+    P = (x.shape[2] + 2 * padding - 3) // stride + 1
+    Q = (x.shape[3] + 2 * padding - 3) // stride + 1
+    return P * Q >= 28 * 28 and x.shape[0] * x.shape[1] * P * Q >= 25_000_000
+
+
+def depthwise_conv2d(x, w, stride: int = 1, padding: int = 0,
+                     want_stats: bool = False):
     """Depthwise conv: x (N,C,H,W), w (C,1,k,k), groups == C.
 
     GPU bf16/fp16 3x3 cases inside the kernel envelope run the hand HIP
     depthwise kernels; everything else (CPU, fp32, C % 8 != 0, other kernel
-    sizes, DTMX_FALLBACK=dwconv) is torch's grouped conv."""
+    sizes, DTMX_FALLBACK=dwconv) is torch's grouped conv.
+
+    want_stats: return (y, psum, psumsq) as DF.conv2d does — the following
+    BatchNorm's statistic slabs, written by the conv kernel itself
+    (dwconv_fwd_stats). The slabs are empty wherever the call does not take
+    that kernel: the torch path, or a class _dwconv_stats_routed gates out."""
     if _use_hip(x, w, op="dwconv") and _dwconv_in_envelope(x, w, stride, padding):
         x = x.contiguous(memory_format=torch.channels_last)
-        return _DepthwiseConvNHWC.apply(x, w, stride, padding)
-    return F.conv2d(x, w, None, stride, padding, 1, x.shape[1])
+        if want_stats and _dwconv_stats_routed(x, w, stride, padding):
+            return _DepthwiseConvNHWC.apply(x, w, stride, padding, True)
+        y = _DepthwiseConvNHWC.apply(x, w, stride, padding)
+    else:
+        y = F.conv2d(x, w, None, stride, padding, 1, x.shape[1])
+    if want_stats:
+        z = y.new_zeros(0, dtype=torch.float32)
+        return y, z, z
+    return y
 
 
 # ------------------------------------------------------------- grouped conv
@@ -395,16 +429,20 @@ class _GroupedConvNHWC(torch.autograd.Function):
     contiguous or channels_last; dw comes back in the same layout."""
 
     @staticmethod
-    def forward(ctx, x, w, stride, padding, groups):
+    def forward(ctx, x, w, stride, padding, groups, want_stats=False):
         ext = require_ext()
         ctx.save_for_backward(x, w)
         ctx.stride = stride
         ctx.padding = padding
         ctx.groups = groups
-        return ext.gconv_fwd(x, w, stride, padding, groups)
+        if not want_stats:
+            return ext.gconv_fwd(x, w, stride, padding, groups)
+        y, ps, pss = ext.gconv_fwd_stats(x, w, stride, padding, groups)
+        ctx.mark_non_differentiable(ps, pss)
+        return y, ps, pss
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, _dps=None, _dpss=None):
         ext = require_ext()
         x, w = ctx.saved_tensors
         dy = dy.contiguous(memory_format=torch.channels_last)
@@ -415,7 +453,7 @@ class _GroupedConvNHWC(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dw = ext.gconv_wgrad(x, dy, ctx.stride, ctx.padding, ctx.groups,
                                  not w.is_contiguous())
-        return dx, dw, None, None, None
+        return dx, dw, None, None, None, None
 
 
 def _gconv_in_envelope(x, w, stride, padding, groups) -> bool:
@@ -439,18 +477,41 @@ def _gconv_in_envelope(x, w, stride, padding, groups) -> bool:
             and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
 
 
-def grouped_conv2d(x, w, stride: int = 1, padding: int = 0, groups: int = 1):
+def _gconv_stats_routed(x, w, stride, padding, groups) -> bool:
+    """Shape classes where gconv_fwd_stats plus the slab reduce measured
+    faster than gconv_fwd plus the BatchNorm's own statistics pass by more
+    than the run-to-run spread (tools/bench_gconv.py --stats, profiles/
+    resnext_mi355x.md): all seven ResNeXt-50 conv2 shapes won 12-17 % at
+    batch 1024 with a spread under 1 %, and gconv_fwd_stats is as fast as
+    gconv_fwd on each, so the whole envelope is routed."""
+    return True
+
+
+def grouped_conv2d(x, w, stride: int = 1, padding: int = 0, groups: int = 1,
+                   want_stats: bool = False):
     """Grouped conv: x (N,C,H,W), w (C_out, C/groups, k, k).
 
     GPU bf16/fp16 3x3 cases inside the kernel envelope run the hand HIP
     grouped kernels; everything else (CPU, fp32, other channel counts or
     kernel sizes, C_in != C_out, DTMX_FALLBACK=gconv) is torch's grouped
-    conv. Depthwise (one channel per group) belongs to depthwise_conv2d."""
+    conv. Depthwise (one channel per group) belongs to depthwise_conv2d.
+
+    want_stats: return (y, psum, psumsq) as DF.conv2d does — the following
+    BatchNorm's statistic slabs, written by the conv kernel itself
+    (gconv_fwd_stats). The slabs are empty wherever the call does not take
+    that kernel: the torch path, or a class _gconv_stats_routed gates out."""
     if _use_hip(x, w, op="gconv") and _gconv_in_envelope(x, w, stride, padding,
                                                         groups):
         x = x.contiguous(memory_format=torch.channels_last)
-        return _GroupedConvNHWC.apply(x, w, stride, padding, groups)
-    return F.conv2d(x, w, None, stride, padding, 1, groups)
+        if want_stats and _gconv_stats_routed(x, w, stride, padding, groups):
+            return _GroupedConvNHWC.apply(x, w, stride, padding, groups, True)
+        y = _GroupedConvNHWC.apply(x, w, stride, padding, groups)
+    else:
+        y = F.conv2d(x, w, None, stride, padding, 1, groups)
+    if want_stats:
+        z = y.new_zeros(0, dtype=torch.float32)
+        return y, z, z
+    return y
 
 
 # --------------------------------------------------------------- batch norm

@@ -131,12 +131,26 @@ class GroupedConv2dNHWC(nn.Module):
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
 
     def forward(self, x):
+        # as Conv2dNHWC: a bias-free training conv hands the following
+        # BatchNorm its statistic slabs (dwconv_fwd_stats / gconv_fwd_stats);
+        # DTMX_FUSE_BN_STATS=0 restores the standalone stats pass
+        import os as _os
+        w = self.weight.to(x.dtype)
+        if (self.bias is None and x.is_cuda and self.training
+                and _os.environ.get("DTMX_FUSE_BN_STATS", "1") == "1"):
+            if self.depthwise:
+                y, ps, pss = DF.depthwise_conv2d(x, w, self.stride, self.padding,
+                                                 want_stats=True)
+            else:
+                y, ps, pss = DF.grouped_conv2d(x, w, self.stride, self.padding,
+                                               self.groups, want_stats=True)
+            if ps.numel():
+                y._dtmx_bn_stats = (ps, pss)
+            return y
         if self.depthwise:
-            y = DF.depthwise_conv2d(x, self.weight.to(x.dtype), self.stride,
-                                    self.padding)
+            y = DF.depthwise_conv2d(x, w, self.stride, self.padding)
         else:
-            y = DF.grouped_conv2d(x, self.weight.to(x.dtype), self.stride,
-                                  self.padding, self.groups)
+            y = DF.grouped_conv2d(x, w, self.stride, self.padding, self.groups)
         if self.bias is not None:
             y = y + self.bias.reshape(1, -1, 1, 1).to(y.dtype)
         return y

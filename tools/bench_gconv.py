@@ -103,16 +103,75 @@ def time_ms(fn, iters):
     return a.elapsed_time(b) / iters
 
 
+def stats_ok(y, ps, pss, y_plain):
+    """At the timed shape: y equals the plain entry's bits and the slab
+    column totals are the fp64 sums over y within n * 2^-24 * sum|v|."""
+    v = y.double().permute(1, 0, 2, 3).reshape(y.shape[1], -1)
+    u = v.shape[1] * 2.0 ** -24
+    return bool(torch.equal(y, y_plain)
+                and ((ps.double().sum(0) - v.sum(1)).abs() <= u * v.abs().sum(1)).all()
+                and ((pss.double().sum(0) - (v * v).sum(1)).abs()
+                     <= u * (v * v).sum(1)).all())
+
+
+def bench_stats(ext, args):
+    """Forward + the following training BatchNorm (fused ReLU, packed mask):
+    gconv_fwd_stats feeding bn_fwd_train its slabs, against the parent's
+    gconv_fwd and the BatchNorm's own statistics pass. Also the two conv
+    kernels alone, and the fused kernel's GB/s over x + y + both slabs."""
+    print(f"batch {args.batch}, bf16 NHWC, groups {GROUPS}, pad 1; median "
+          f"[min .. max] of {args.rounds} alternating rounds x {args.iters} calls")
+    print("| C | H=W | s | fwd ms | fwd_stats ms | stats GB/s | slab rows | "
+          "fwd + BN ms | fwd_stats + BN ms | parent/new |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for C, H, stride in SHAPES:
+        x, _, w, _ = make(args.batch, C, H, stride)
+        g, b = torch.ones(C, device=DEV).bfloat16(), torch.zeros(C, device=DEV).bfloat16()
+        rm, rv = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+
+        def bn(y, ps=None, pss=None):
+            return ext.bn_fwd_train(y, g, b, rm, rv, 0.9, 1e-5, True, None, ps, pss, True)
+
+        fns = {
+            "fwd": lambda: ext.gconv_fwd(x, w, stride, PAD, GROUPS),
+            "fwd_stats": lambda: ext.gconv_fwd_stats(x, w, stride, PAD, GROUPS),
+            "old": lambda: bn(ext.gconv_fwd(x, w, stride, PAD, GROUPS)),
+            "new": lambda: bn(*ext.gconv_fwd_stats(x, w, stride, PAD, GROUPS)),
+        }
+        y, ps, pss = fns["fwd_stats"]()
+        if not stats_ok(y, ps, pss, fns["fwd"]()):
+            sys.exit(f"bench_gconv: stats check failed C={C} H={H} s={stride}")
+        nbytes = (x.numel() + y.numel()) * 2 + 2 * ps.numel() * 4
+        for _ in range(3):
+            for f in fns.values():
+                f()
+        torch.cuda.synchronize()
+        t = {k: [] for k in fns}
+        for _ in range(args.rounds):
+            for k, f in fns.items():
+                t[k].append(time_ms(f, args.iters))
+        med = {k: statistics.median(v) for k, v in t.items()}
+        cell = lambda k: f"{med[k]:.4f} [{min(t[k]):.4f} .. {max(t[k]):.4f}]"
+        print(f"| {C} | {H} | {stride} | {cell('fwd')} | {cell('fwd_stats')} | "
+              f"{nbytes / (med['fwd_stats'] * 1e-3) / 1e9:.0f} | {ps.shape[0]} | "
+              f"{cell('old')} | {cell('new')} | {med['old'] / med['new']:.3f}x |",
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--stats", action="store_true",
+                    help="time the fused BN-statistics forward instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_gconv: needs a GPU")
     from dtmx.ops.hip import require_ext
     ext = require_ext()
+    if args.stats:
+        return bench_stats(ext, args)
 
     if not refcheck(ext):
         sys.exit("bench_gconv: refcheck failed, no timings")
