@@ -148,6 +148,12 @@ at::Tensor gemm256_nt(const at::Tensor&, const at::Tensor&);
 at::Tensor gemm256n_nt(const at::Tensor&, const at::Tensor&);
 at::Tensor lrn_fwd(const at::Tensor&, double, double, double);
 at::Tensor lrn_bwd(const at::Tensor&, const at::Tensor&, double, double, double);
+// fused bias + ReLU: forward entries (gemm_conv.hip), backward (biasact.hip)
+at::Tensor conv_fwd_act(const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                        bool, long, long, long);
+at::Tensor linear_fwd_act(const at::Tensor&, const at::Tensor&,
+                          const at::Tensor&, bool);
+std::vector<at::Tensor> bias_act_bwd(const at::Tensor&, const at::Tensor&, bool);
 // indexing.hip
 at::Tensor take_fwd(const at::Tensor&, const at::Tensor&);
 at::Tensor take_bwd(const at::Tensor&, const at::Tensor&, long);
@@ -175,6 +181,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_dgrad_hw", &dtmx::conv_dgrad_hw, py::arg("dy"), py::arg("w"),
         py::arg("stride"), py::arg("pad_h"), py::arg("pad_w"), py::arg("H"),
         py::arg("W"));
+  // Bias add and ReLU in the GEMM epilogue of conv_fwd / conv_fwd_hw /
+  // linear_fwd's routing: round16(relu(round16(acc) + bias)) on every route.
+  m.def("conv_fwd_act", &dtmx::conv_fwd_act, py::arg("x"), py::arg("w"),
+        py::arg("bias"), py::arg("relu"), py::arg("stride"), py::arg("pad_h"),
+        py::arg("pad_w"));
+  m.def("linear_fwd_act", &dtmx::linear_fwd_act, py::arg("x"), py::arg("w"),
+        py::arg("bias"), py::arg("relu"));
+  // (g, db32): g = y > 0 ? dy : 0 and db32[c] = sum over rows of g in one
+  // pass over a dense [rows][C] buffer; relu = false: g is dy, y is unread.
+  m.def("bias_act_bwd", &dtmx::bias_act_bwd, py::arg("dy"), py::arg("y"),
+        py::arg("relu"));
   m.def("conv_wgrad_hw", &dtmx::conv_wgrad_hw, py::arg("x"), py::arg("dy"),
         py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad_h"),
         py::arg("pad_w"));

@@ -1907,6 +1907,32 @@ __global__ void cast_f32_bf16_kernel(const float* __restrict__ in,
   }
 }
 
+// finisher of the small-grid split-K route for the fused bias + ReLU forward
+// (conv_fwd_act): the two roundings of EpiBF16::store_chunk — accumulator to
+// 16 bits, plus the fp32 bias, (ReLU,) to 16 bits again — so every route
+// stores the bits of conv store -> 16-bit add -> ReLU. n8 = N / 8.
+template <typename elem_t>
+__global__ void cast_f32_bf16_bias_act_kernel(const float* __restrict__ in,
+                                              elem_t* __restrict__ out,
+                                              const float* __restrict__ bias,
+                                              uint32_t n8, int relu,
+                                              size_t total8) {
+  using V8 = typename E8<elem_t>::v8;
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < total8; i += stride) {
+    const uint32_t n0 = (uint32_t)(i % n8) * 8;
+    V8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float f = (float)(elem_t)in[i * 8 + e] + (bias ? bias[n0 + e] : 0.f);
+      if (relu) f = fmaxf(f, 0.f);
+      o[e] = (elem_t)f;
+    }
+    *(V8*)(out + i * 8) = o;
+  }
+}
+
 // drain-and-rezero variant for the persistent wgrad split-K accumulator:
 // casting is the only consumer, so zeroing here replaces a separate fill
 // before every wgrad launch (the fills were pure launch overhead, ~50/step).
@@ -2235,8 +2261,9 @@ static at::Tensor pad_cols8(const at::Tensor& t) {
   return at::constant_pad_nd(t, {0, 8 - (k % 8)}, 0.0).contiguous();
 }
 
-at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w,
-                      const c10::optional<at::Tensor>& bias) {
+static at::Tensor linear_fwd_impl(const at::Tensor& x, const at::Tensor& w,
+                                  const c10::optional<at::Tensor>& bias,
+                                  int relu) {
   DTMX_DISPATCH_16(x.scalar_type(), "linear_fwd", {
     CHECK_BF16_CUDA(x);
     CHECK_BF16_CUDA(w);
@@ -2254,12 +2281,35 @@ at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w,
     }
     DenseP<elem_t> pa{(const elem_t*)xc.data_ptr(), zero_page<elem_t>(x), M, K, K};
     DenseP<elem_t> pb{(const elem_t*)wc.data_ptr(), zero_page<elem_t>(x), N, K, K};
-    EpiBF16<elem_t> epi{(elem_t*)y.data_ptr(), bp, M, N, 0};
+    EpiBF16<elem_t> epi{(elem_t*)y.data_ptr(), bp, M, N, relu};
     launch_gemm(pa, pb, epi, M, N, K);
     return y;
 
   });
   return at::Tensor();
+}
+
+at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w,
+                      const c10::optional<at::Tensor>& bias) {
+  return linear_fwd_impl(x, w, bias, 0);
+}
+
+// y = act(x @ w^T + bias) with the bias add and the ReLU in the GEMM epilogue:
+// round16(relu(round16(acc) + bias)), the bits of linear_fwd without a bias
+// -> 16-bit add -> relu_fwd.
+at::Tensor linear_fwd_act(const at::Tensor& x, const at::Tensor& w,
+                          const at::Tensor& bias, bool relu) {
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2,
+              "linear_fwd_act: x must be (M, K) and w (N, K)");
+  TORCH_CHECK(w.scalar_type() == x.scalar_type() && w.device() == x.device(),
+              "linear_fwd_act: w must be on the device of x and of its dtype");
+  TORCH_CHECK(bias.is_cuda() && bias.device() == x.device() &&
+                  bias.dim() == 1 && bias.size(0) == w.size(0),
+              "linear_fwd_act: bias must be a GPU vector of w.size(0) = ",
+              w.size(0), " elements");
+  TORCH_CHECK(x.size(0) > 0 && w.size(0) > 0 && x.size(1) > 0,
+              "linear_fwd_act: empty operand");
+  return linear_fwd_impl(x, w, bias, relu ? 1 : 0);
 }
 
 template <typename elem_t>
@@ -2345,7 +2395,8 @@ std::tuple<bool, long> smallgrid_plan(long M, long N, long K) {
 // underfills the chip (e.g. the 7x7 resnet stage: 196 blocks on 256 CUs).
 template <class PA, class PB>
 static bool smallgrid_splitk(const PA& pa, const PB& pb, at::Tensor& out_bf16,
-                             uint32_t M, uint32_t N, uint32_t K) {
+                             uint32_t M, uint32_t N, uint32_t K,
+                             const float* bias = nullptr, int relu = 0) {
   using elem_t = typename PA::elem;
   const uint32_t splitk = smallgrid_splitk_of(M, N, K);
   if (!splitk) return false;
@@ -2353,16 +2404,24 @@ static bool smallgrid_splitk(const PA& pa, const PB& pb, at::Tensor& out_bf16,
   EpiAtomicF32<elem_t> epi{acc.data_ptr<float>(), M, N};
   launch_gemm(pa, pb, epi, M, N, K, splitk);
   size_t t8 = (size_t)M * N / 8;  // N % 8 == 0 everywhere this is used
-  cast_f32_bf16_kernel<<<std::min<size_t>((t8 + 255) / 256, 2048), 256, 0,
-                         cur_stream()>>>(acc.data_ptr<float>(),
-                                         (elem_t*)out_bf16.data_ptr(), t8);
+  if (bias || relu)  // the atomic epilogue carries neither: finish them here
+    cast_f32_bf16_bias_act_kernel<<<std::min<size_t>((t8 + 255) / 256, 2048),
+                                    256, 0, cur_stream()>>>(
+        acc.data_ptr<float>(), (elem_t*)out_bf16.data_ptr(), bias, N / 8, relu,
+        t8);
+  else
+    cast_f32_bf16_kernel<<<std::min<size_t>((t8 + 255) / 256, 2048), 256, 0,
+                           cur_stream()>>>(acc.data_ptr<float>(),
+                                           (elem_t*)out_bf16.data_ptr(), t8);
   return true;
 }
 
 // (ph, pw) = padding of the H and of the W axis; the public square forms
-// pass pad twice
+// pass pad twice. bias (fp32 [Ko], nullable) and relu ride the EpiBF16
+// epilogue of whichever kernel the shape routes to (conv_fwd_act).
 static at::Tensor conv_fwd_impl(const at::Tensor& x, const at::Tensor& w,
-                                long stride, long ph, long pw) {
+                                long stride, long ph, long pw,
+                                const float* bias = nullptr, int relu = 0) {
   DTMX_DISPATCH_16(x.scalar_type(), "conv_fwd", {
     CHECK_BF16_CUDA(x);
     CHECK_BF16_CUDA(w);
@@ -2375,12 +2434,12 @@ static at::Tensor conv_fwd_impl(const at::Tensor& x, const at::Tensor& w,
     auto y = at::empty({(long)N, (long)Ko, (long)P, (long)Q},
                        x.options(), at::MemoryFormat::ChannelsLast);
     uint32_t M = N * P * Q, Ktot = R * S * C;
-    EpiBF16<elem_t> epi{(elem_t*)y.data_ptr(), nullptr, M, Ko, 0};
+    EpiBF16<elem_t> epi{(elem_t*)y.data_ptr(), bias, M, Ko, relu};
     if (R == 1 && S == 1 && stride == 1 && ph == 0 && pw == 0 && C % 8 == 0) {
       // 1x1/s1: the im2col matrix IS x — pure dense GEMM, no gather decode
       DenseP<elem_t> pa{(const elem_t*)x.data_ptr(), zero_page<elem_t>(x), M, C, C};
       DenseP<elem_t> pb{(const elem_t*)w.data_ptr(), zero_page<elem_t>(x), Ko, C, C};
-      if (!smallgrid_splitk(pa, pb, y, M, Ko, C))
+      if (!smallgrid_splitk(pa, pb, y, M, Ko, C, bias, relu))
         launch_gemm(pa, pb, epi, M, Ko, C);
     } else if (C % 8 == 0) {
       DenseP<elem_t> pb{(const elem_t*)w.data_ptr(), zero_page<elem_t>(x), Ko, Ktot, Ktot};
@@ -2390,7 +2449,7 @@ static at::Tensor conv_fwd_impl(const at::Tensor& x, const at::Tensor& w,
       pa.M = M; pa.Ktot = Ktot; pa.C = C; pa.H = H; pa.W = W_; pa.Q = Q; pa.S = S;
       pa.u = stride; pa.v = stride; pa.ph = ph; pa.pw = pw;
       pa.dQ.init(Q); pa.dPQ.init(P * Q); pa.dC.init(C); pa.dS.init(S);
-      if (!smallgrid_splitk(pa, pb, y, M, Ko, Ktot))
+      if (!smallgrid_splitk(pa, pb, y, M, Ko, Ktot, bias, relu))
         launch_gemm(pa, pb, epi, M, Ko, Ktot);
     } else {
       // small-C path (3-channel stem): materialized im2col, then dense GEMM.
@@ -2470,6 +2529,44 @@ at::Tensor conv_fwd_hw(const at::Tensor& x, const at::Tensor& w, long stride,
   conv_hw_check("conv_fwd_hw", "x", x, w, false, stride, ph, pw, x.size(2),
                 x.size(3));
   return conv_fwd_impl(x, w, stride, ph, pw);
+}
+
+// conv forward with the bias add and the ReLU in the GEMM epilogue, on the
+// routing of conv_fwd (pad_h == pad_w, square window; C % 8 != 0 takes the
+// im2col branch) or of conv_fwd_hw (per-axis / rectangular). Every route
+// stores round16(relu(round16(acc) + bias)): the bits of conv_fwd -> 16-bit
+// broadcast add -> relu_fwd. The bias is rounded to the activation dtype
+// first, as that add does. Ko % 8 == 0 (the split-K finisher and the callers'
+// bias_act_bwd work on 16-byte channel vectors).
+at::Tensor conv_fwd_act(const at::Tensor& x, const at::Tensor& w,
+                        const at::Tensor& bias, bool relu, long stride,
+                        long ph, long pw) {
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4,
+              "conv_fwd_act: x must be (N,C,H,W) and w (Ko,C,R,S)");
+  CHECK_BF16_CUDA(x);
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == x.scalar_type() &&
+                  w.device() == x.device(),
+              "conv_fwd_act: w must be on the device of x and of its dtype");
+  const long Ko = w.size(0), R = w.size(2), S = w.size(3);
+  TORCH_CHECK(Ko % 8 == 0, "conv_fwd_act: Ko % 8 == 0 required, got Ko = ", Ko);
+  TORCH_CHECK(bias.is_cuda() && bias.device() == x.device() &&
+                  bias.dim() == 1 && bias.size(0) == Ko,
+              "conv_fwd_act: bias must be a GPU vector of Ko = ", Ko, " elements");
+  if (R != S || ph != pw) {
+    conv_hw_check("conv_fwd_act", "x", x, w, false, stride, ph, pw, x.size(2),
+                  x.size(3));
+  } else {
+    TORCH_CHECK(x.size(1) == w.size(1), "conv_fwd_act: x has ", x.size(1),
+                " channels, w wants ", w.size(1));
+    TORCH_CHECK(stride >= 1 && ph >= 0 && x.numel() > 0 &&
+                    x.size(2) + 2 * ph >= R && x.size(3) + 2 * pw >= S,
+                "conv_fwd_act: the ", R, "x", S,
+                " window does not fit the padded input (stride ", stride,
+                ", pad ", ph, ")");
+  }
+  auto bias_f = bias.to(x.scalar_type()).to(at::kFloat).contiguous();
+  return conv_fwd_impl(x, w, stride, ph, pw, bias_f.data_ptr<float>(),
+                       relu ? 1 : 0);
 }
 
 // conv forward with fused BN statistics: returns (y, psum, psumsq) where the

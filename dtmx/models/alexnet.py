@@ -4,8 +4,7 @@ from __future__ import annotations
 
 import torch.nn as nn
 
-from ..ops.layers import (LRN, Conv2dNHWC, Dropout, LinearBF16,
-                          MaxPool2dNHWC, ReLU)
+from ..ops.layers import LRN, Conv2dNHWC, Dropout, LinearBF16, MaxPool2dNHWC
 
 
 class AlexNet(nn.Module):
@@ -15,18 +14,21 @@ class AlexNet(nn.Module):
         self.features = nn.Sequential(
             # LRN after the first two relus per the reference symbol
             # (alexnet.py:34,41 — mx.sym.LRN alpha=1e-4 beta=0.75 knorm=2
-            # nsize=5); kept in the benchmarked graph
-            Conv2dNHWC(3, 64, 11, 4, 2, bias=True), ReLU(), LRN(),
+            # nsize=5); kept in the benchmarked graph. The ReLUs ride the
+            # convs and FCs (relu=True); an Identity stands where each sat, so
+            # the Sequential indices and the state_dict keys are unchanged.
+            Conv2dNHWC(3, 64, 11, 4, 2, bias=True, relu=True), nn.Identity(), LRN(),
             MaxPool2dNHWC(3, 2),
-            Conv2dNHWC(64, 192, 5, 1, 2, bias=True), ReLU(), LRN(),
+            Conv2dNHWC(64, 192, 5, 1, 2, bias=True, relu=True), nn.Identity(), LRN(),
             MaxPool2dNHWC(3, 2),
-            Conv2dNHWC(192, 384, 3, 1, 1, bias=True), ReLU(),
-            Conv2dNHWC(384, 256, 3, 1, 1, bias=True), ReLU(),
-            Conv2dNHWC(256, 256, 3, 1, 1, bias=True), ReLU(), MaxPool2dNHWC(3, 2),
+            Conv2dNHWC(192, 384, 3, 1, 1, bias=True, relu=True), nn.Identity(),
+            Conv2dNHWC(384, 256, 3, 1, 1, bias=True, relu=True), nn.Identity(),
+            Conv2dNHWC(256, 256, 3, 1, 1, bias=True, relu=True), nn.Identity(),
+            MaxPool2dNHWC(3, 2),
         )
         self.classifier = nn.Sequential(
-            LinearBF16(256 * 6 * 6, 4096), ReLU(), Dropout(0.5),
-            LinearBF16(4096, 4096), ReLU(), Dropout(0.5),
+            LinearBF16(256 * 6 * 6, 4096, relu=True), nn.Identity(), Dropout(0.5),
+            LinearBF16(4096, 4096, relu=True), nn.Identity(), Dropout(0.5),
             LinearBF16(4096, num_classes),
         )
 

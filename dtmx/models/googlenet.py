@@ -7,18 +7,17 @@ import torch
 import torch.nn as nn
 
 from ..ops.layers import (Conv2dNHWC, Dropout, GlobalAvgPool, LinearBF16,
-                          MaxPool2dNHWC, ReLU)
+                          MaxPool2dNHWC)
 
 
 class ConvRelu(nn.Module):
     def __init__(self, cin, cout, k, stride=1, pad=0):
         super().__init__()
         self.conv = Conv2dNHWC(cin, cout, k, stride=stride, padding=pad,
-                               bias=True)
-        self.act = ReLU()
+                               bias=True, relu=True)
 
     def forward(self, x):
-        return self.act(self.conv(x))
+        return self.conv(x)
 
 
 class Inception(nn.Module):

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import torch.nn as nn
 
-from ..ops.layers import Conv2dNHWC, Dropout, LinearBF16, MaxPool2dNHWC, ReLU
+from ..ops.layers import Conv2dNHWC, Dropout, LinearBF16, MaxPool2dNHWC
 
 _CFG = {
     11: [64, "M", 128, "M", 256, 256, "M", 512, 512, "M", 512, 512, "M"],
@@ -25,12 +25,15 @@ class VGG(nn.Module):
             if v == "M":
                 layers.append(MaxPool2dNHWC(2, 2))
             else:
-                layers += [Conv2dNHWC(in_ch, v, 3, 1, 1, bias=True), ReLU()]
+                # the ReLU rides the conv (DF.conv2d_bias_act); the Identity
+                # keeps the Sequential indices, hence the state_dict keys
+                layers += [Conv2dNHWC(in_ch, v, 3, 1, 1, bias=True, relu=True),
+                           nn.Identity()]
                 in_ch = v
         self.features = nn.Sequential(*layers)
         self.classifier = nn.Sequential(
-            LinearBF16(512 * 7 * 7, 4096), ReLU(), Dropout(0.5),
-            LinearBF16(4096, 4096), ReLU(), Dropout(0.5),
+            LinearBF16(512 * 7 * 7, 4096, relu=True), nn.Identity(), Dropout(0.5),
+            LinearBF16(4096, 4096, relu=True), nn.Identity(), Dropout(0.5),
             LinearBF16(4096, num_classes),
         )
 

@@ -333,6 +333,121 @@ def conv2d(x, w, stride: int = 1, padding=0, want_stats: bool = False):
     return F.conv2d(x, w, None, stride, padding)
 
 
+# ------------------------------------------------- conv + bias (+ ReLU) fused
+
+class _ConvBiasAct(torch.autograd.Function):
+    """conv -> + bias -> (ReLU) with the bias and the ReLU in the GEMM epilogue
+    (ext.conv_fwd_act) and one backward pass, ext.bias_act_bwd, for the masked
+    gradient and the bias gradient; g then feeds the dgrad / wgrad entries
+    DF.conv2d would reach. `x` and `w` are the operands as stored: a C % 8 != 0
+    input is zero-padded to 8 channels for the generic kernels, as DF.conv2d
+    does, and a first layer in the stem envelope takes stemconv_wgrad on the
+    unpadded x."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, relu, stride, ph, pw, stem):
+        ext = require_ext()
+        C = x.shape[1]
+        padc = (0, 0, 0, 0, 0, -C % 8)
+        x8 = (F.pad(x, padc) if C % 8 else x).contiguous(
+            memory_format=torch.channels_last)
+        w8 = (F.pad(w, padc) if C % 8 else w).contiguous(
+            memory_format=torch.channels_last)
+        if _biasact_fwd_routed(ext, x8, w8, stride, ph, pw):
+            y = ext.conv_fwd_act(x8, w8, bias, relu, stride, ph, pw)
+        else:  # the same bits in three passes
+            y = (ext.conv_fwd(x8, w8, stride, ph)
+                 if w.shape[2] == w.shape[3] and ph == pw
+                 else ext.conv_fwd_hw(x8, w8, stride, ph, pw))
+            y.add_(bias.reshape(1, -1, 1, 1).to(y.dtype))
+            y = ext.relu_fwd(y) if relu else y
+        ctx.save_for_backward(x if stem else x8, w if stem else w8,
+                              y if relu else None)
+        ctx.conv = (relu, stride, ph, pw, stem, C, bias.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = require_ext()
+        x, w, y = ctx.saved_tensors
+        relu, stride, ph, pw, stem, C, bias_dtype = ctx.conv
+        R, S = w.shape[2:]
+        square = R == S and ph == pw
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = _aligned(_to_layout_of(dy, y) if relu else dy)
+        g, db32 = ext.bias_act_bwd(dy, y if relu else dy, relu)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            w8 = F.pad(w, (0, 0, 0, 0, 0, -C % 8)).contiguous(
+                memory_format=torch.channels_last) if stem else w
+            H, W = x.shape[2:]
+            dx = (ext.conv_dgrad(g, w8, stride, ph, H, W) if square else
+                  ext.conv_dgrad_hw(g, w8, stride, ph, pw, H, W))
+            if C % 8:
+                dx = dx[:, :C].contiguous(memory_format=torch.channels_last)
+        if ctx.needs_input_grad[1]:
+            if stem:
+                dw = ext.stemconv_wgrad(x, g, R, S, stride, ph, pw,
+                                        not w.is_contiguous())
+            else:
+                dw = (ext.conv_wgrad(x, g, R, S, stride, ph) if square else
+                      ext.conv_wgrad_hw(x, g, R, S, stride, ph, pw))[:, :C]
+        db = db32.to(bias_dtype) if ctx.needs_input_grad[2] else None
+        return dx, dw, db, None, None, None, None, None
+
+
+def _biasact_fwd_routed(ext, x8, w8, stride, ph, pw) -> bool:
+    """Whether a call inside _biasact_routed also takes the fused FORWARD
+    (the backward pass is routed on its own). Every shape that the GEMM plan
+    sends to gemm256f_kernel lost with the bias in its epilogue
+    (tools/bench_biasact.py, batch 128, unfused / fused forward: VGG 256@56
+    0.963x, 512@28 0.967x, 512@14 0.955x, AlexNet conv2 0.915x, conv3 0.890x),
+    so those run conv -> add -> relu; the tn<2>, tn<4> and split-K routes won
+    or tied (0.97x .. 1.62x, the losses inside their rows' spread).
+    profiles/vgg_mi355x.md has the table and the reasoning."""
+    Ko, C, R, S = w8.shape
+    N, _, H, W = x8.shape
+    M = N * ((H + 2 * ph - R) // stride + 1) * ((W + 2 * pw - S) // stride + 1)
+    return ext.gemm_plan(M, Ko, R * S * C)[0] != 256
+
+
+def _biasact_routed(x, w, bias, stride, ph, pw) -> bool:
+    """The calls that take the fused bias + ReLU path: GPU bf16/fp16 with a
+    bias and Ko % 8 == 0 (LeNet's 20 and 50 channels stay unfused), outside
+    the line kernels' routing (lineconv.hip has an epilogue of its own).
+    DTMX_FALLBACK=biasact restores conv -> add -> relu everywhere.
+    profiles/vgg_mi355x.md holds the measurements behind the routing."""
+    if (bias is None or "biasact" in _FALLBACK or w.shape[0] % 8 != 0
+            or not isinstance(stride, int)
+            or not _use_hip(x, op="conv") or w.dtype != x.dtype):
+        return False
+    if (w.shape[2] != w.shape[3] or ph != pw) and x.shape[1] % 8 == 0:
+        wl = w.contiguous(memory_format=torch.channels_last)
+        xl = x.contiguous(memory_format=torch.channels_last)
+        if "lineconv" not in _FALLBACK and _lineconv_routed(xl, wl, stride, ph, pw):
+            return False
+    return True
+
+
+def conv2d_bias_act(x, w, bias, relu: bool = True, stride: int = 1, padding=0):
+    """relu(conv2d(x, w) + bias) (relu=False: conv2d(x, w) + bias); padding as
+    DF.conv2d. On the GPU in bf16/fp16 (_biasact_routed) the bias add and the
+    ReLU ride the conv's GEMM epilogue, bit-identical to the three-op
+    sequence, and backward makes one pass for the masked gradient and the
+    bias gradient. Everything else (CPU, fp32, Ko % 8 != 0, line-routed 1xT /
+    Tx1 calls, DTMX_FALLBACK=biasact) runs conv -> add -> relu."""
+    ph, pw = ((padding, padding) if isinstance(padding, int)
+              else (int(p) for p in padding))
+    if _biasact_routed(x, w, bias, stride, ph, pw):
+        stem = ("stemconv" not in _FALLBACK
+                and _stemconv_routed(x, w, stride, ph, pw))
+        return _ConvBiasAct.apply(x, w, bias, relu, stride, ph, pw, stem)
+    y = conv2d(x, w, stride, padding)
+    if bias is not None:
+        y = y + bias.reshape(1, -1, 1, 1).to(y.dtype)
+    return _relu(y) if relu else y
+
+
 # ----------------------------------------------------------- depthwise conv
 
 class _DepthwiseConvNHWC(torch.autograd.Function):
@@ -756,6 +871,9 @@ def relu(x):
     return F.relu(x)
 
 
+_relu = relu  # for the functions whose own argument is named relu
+
+
 class _AddRelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -830,11 +948,46 @@ class _Linear(torch.autograd.Function):
         return dx, dw, db
 
 
-def linear(x, w, bias=None):
-    """x:(M,K) w:(N,K) -> (M,N)   (FullyConnected: X @ W^T + b)"""
+class _LinearAct(torch.autograd.Function):
+    """relu(x @ w^T + bias) with the ReLU in the GEMM epilogue beside the bias
+    (ext.linear_fwd_act) and one backward pass (ext.bias_act_bwd) for the
+    masked gradient and the bias gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        y = require_ext().linear_fwd_act(x, w, bias, True)
+        ctx.save_for_backward(x, w, y)
+        ctx.bias_dtype = bias.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = require_ext()
+        x, w, y = ctx.saved_tensors
+        g, db32 = ext.bias_act_bwd(_aligned(dy.contiguous()), y, True)
+        dx = ext.linear_dgrad(g, w) if ctx.needs_input_grad[0] else None
+        dw = ext.linear_wgrad(g, x) if ctx.needs_input_grad[1] else None
+        db = db32.to(ctx.bias_dtype) if ctx.needs_input_grad[2] else None
+        return dx, dw, db
+
+
+def linear(x, w, bias=None, relu: bool = False):
+    """x:(M,K) w:(N,K) -> (M,N)   (FullyConnected: X @ W^T + b)
+
+    relu=True: relu(X @ W^T + b). On the GPU in bf16/fp16 with a bias and
+    N % 8 == 0 that is one fused forward and one fused backward pass
+    (_LinearAct), bit-identical to linear -> relu; DTMX_FALLBACK=biasact and
+    everything else run the two ops."""
+    if (relu and bias is not None and "biasact" not in _FALLBACK
+            and x.dim() == 2 and w.shape[0] % 8 == 0 and x.numel() > 0
+            and w.dtype == x.dtype
+            and _use_hip(x, w, op="linear")):
+        return _LinearAct.apply(x, w, bias)
     if _use_hip(x, op="linear"):
-        return _Linear.apply(x, w, bias)
-    return F.linear(x, w, bias)
+        y = _Linear.apply(x, w, bias)
+    else:
+        y = F.linear(x, w, bias)
+    return _relu(y) if relu else y
 
 
 # -------------------------------------------------------- fused softmax + CE

@@ -17,11 +17,14 @@ from . import functional as DF
 
 class Conv2dNHWC(nn.Module):
     """kernel_size and padding: an int, or an (h, w) pair (the reference's
-    kernel=(1, 7), pad=(0, 3)); the weight is (Ko, C, R, S)."""
+    kernel=(1, 7), pad=(0, 3)); the weight is (Ko, C, R, S). relu=True (with
+    bias=True: the VGG / AlexNet / GoogLeNet conv) applies ReLU to the output,
+    fused into the conv where DF.conv2d_bias_act fuses it."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0,
-                 bias=False):
+                 bias=False, relu=False):
         super().__init__()
+        self.relu = relu
         self.in_channels = in_channels
         self.out_channels = out_channels
         if isinstance(kernel_size, int):
@@ -48,17 +51,18 @@ class Conv2dNHWC(nn.Module):
         # epilogue (EpiBF16FwdStats) is on by default — DTMX_FUSE_BN_STATS=0
         # restores the standalone stats pass.
         import os as _os
-        if (self.bias is None and x.is_cuda and self.training
+        if (self.bias is None and not self.relu and x.is_cuda and self.training
                 and _os.environ.get("DTMX_FUSE_BN_STATS", "1") == "1"):
             y, ps, pss = DF.conv2d(x, self.weight, self.stride, self.padding,
                                    want_stats=True)
             if ps.numel():
                 y._dtmx_bn_stats = (ps, pss)
             return y
-        y = DF.conv2d(x, self.weight, self.stride, self.padding)
         if self.bias is not None:
-            y = y + self.bias.reshape(1, -1, 1, 1).to(y.dtype)
-        return y
+            return DF.conv2d_bias_act(x, self.weight, self.bias, self.relu,
+                                      self.stride, self.padding)
+        y = DF.conv2d(x, self.weight, self.stride, self.padding)
+        return DF.relu(y) if self.relu else y
 
     def extra_repr(self):
         return (f"{self.in_channels}, {self.out_channels}, k={self.kernel_size}, "
@@ -226,8 +230,9 @@ class LRN(nn.Module):
 
 
 class LinearBF16(nn.Module):
-    def __init__(self, in_features, out_features, bias=True):
+    def __init__(self, in_features, out_features, bias=True, relu=False):
         super().__init__()
+        self.relu = relu
         self.in_features = in_features
         self.out_features = out_features
         w = torch.empty(out_features, in_features)
@@ -236,7 +241,7 @@ class LinearBF16(nn.Module):
         self.bias = nn.Parameter(torch.zeros(out_features)) if bias else None
 
     def forward(self, x):
-        return DF.linear(x, self.weight, self.bias)
+        return DF.linear(x, self.weight, self.bias, relu=self.relu)
 
 
 class Dropout(nn.Module):
