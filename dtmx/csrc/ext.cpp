@@ -51,6 +51,9 @@ at::Tensor gconv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, b
 // lineconv.hip
 at::Tensor lineconv_fwd(const at::Tensor&, const at::Tensor&);
 at::Tensor lineconv_dgrad(const at::Tensor&, const at::Tensor&);
+// lineconv_wgrad.hip
+at::Tensor lineconv_wgrad(const at::Tensor&, const at::Tensor&, long, bool, long);
+std::tuple<long, long> lineconv_wgrad_plan(long, long, long, bool, long, long, long);
 // stemconv.hip
 std::vector<at::Tensor> stemconv_fwd(const at::Tensor&, const at::Tensor&, long, long,
                                      long, bool);
@@ -199,6 +202,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // the (Ko,C,1,T) or (Ko,C,T,1) channels_last parameter
   m.def("lineconv_fwd", &dtmx::lineconv_fwd, py::arg("x"), py::arg("w"));
   m.def("lineconv_dgrad", &dtmx::lineconv_dgrad, py::arg("dy"), py::arg("w"));
+  // dw of the same conv, (Ko,C,1,T) or (Ko,C,T,1) channels_last like
+  // conv_wgrad_hw: fp32 partials per pixel slice, summed in a fixed order.
+  // slices = 0: the plan's count; > 0 forces it (<= ceil(N*H*W / 64)).
+  m.def("lineconv_wgrad", &dtmx::lineconv_wgrad, py::arg("x"), py::arg("dy"),
+        py::arg("T"), py::arg("vertical"), py::arg("slices") = 0);
+  // (tile class = 32-row rounds of the window buffer, slices) the launcher picks
+  m.def("lineconv_wgrad_plan", &dtmx::lineconv_wgrad_plan, py::arg("Ko"),
+        py::arg("C"), py::arg("T"), py::arg("vertical"), py::arg("N"), py::arg("H"),
+        py::arg("W"));
   // First layer, 1 <= C <= 4 input channels read as stored (no padded copy):
   // R <= 7, S <= 8, stride 1|2, pad_h < R, pad_w < S, Ko % 8 == 0; w is the
   // (Ko,C,R,S) parameter in either dense layout. fwd -> [y, psum, psumsq]

@@ -102,13 +102,23 @@ class _ConvHWNHWC(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = ext.conv_dgrad_hw(dy, w, stride, ph, pw, x.shape[2], x.shape[3])
         if ctx.needs_input_grad[1]:
-            dw = ext.conv_wgrad_hw(x, dy, w.shape[2], w.shape[3], stride, ph, pw)
+            dw = _conv_hw_wgrad(ext, x, dy, w, stride, ph, pw)
         return dx, dw, None, None, None
+
+
+def _conv_hw_wgrad(ext, x, dy, w, stride, ph, pw):
+    """dw of a per-axis conv: the line wgrad kernel where it is routed
+    (independently of the forward's routing), else the generic NT kernels."""
+    if not _FALLBACK & {"lineconv", "linewgrad"} and _lineconv_wgrad_routed(
+            x, dy, w, stride, ph, pw):
+        return ext.lineconv_wgrad(x, dy, max(w.shape[2:]), w.shape[3] == 1)
+    return ext.conv_wgrad_hw(x, dy, w.shape[2], w.shape[3], stride, ph, pw)
 
 
 class _LineConvNHWC(torch.autograd.Function):
     """1xT / Tx1 same-padded stride-1 conv on the lineconv.hip kernels (fwd,
-    dgrad); wgrad runs the generic NT kernels."""
+    dgrad); wgrad runs lineconv_wgrad.hip where _lineconv_wgrad_routed says
+    so and the generic NT kernels elsewhere."""
 
     @staticmethod
     def forward(ctx, x, w, ph, pw):
@@ -125,7 +135,7 @@ class _LineConvNHWC(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = ext.lineconv_dgrad(dy, w)
         if ctx.needs_input_grad[1]:
-            dw = ext.conv_wgrad_hw(x, dy, w.shape[2], w.shape[3], 1, *ctx.pad)
+            dw = _conv_hw_wgrad(ext, x, dy, w, 1, *ctx.pad)
         return dx, dw, None, None
 
 
@@ -157,6 +167,42 @@ def _lineconv_routed(x, w, stride, ph, pw) -> bool:
     inception_mi355x.md): every 1xT, and Tx1 while the window fits 160 rows
     ((T-1)*W <= 32, two blocks per CU). The 17x17 7x1 layers lost 6-26 %."""
     if not _lineconv_in_envelope(x, w, stride, ph, pw):
+        return False
+    return w.shape[3] != 1 or (w.shape[2] - 1) * x.shape[3] <= 32
+
+
+def _lineconv_wgrad_in_envelope(x, dy, w, stride, ph, pw) -> bool:
+    """The cases lineconv_wgrad.hip implements: the forward's envelope (the
+    weight only lends its shape), a dy of x's batch and spatial size with Ko
+    channels, and 16-byte aligned NHWC x and dy."""
+    if x.dim() != 4 or dy.dim() != 4 or w.dim() != 4 or stride != 1:
+        return False
+    Ko, C, R, S = w.shape
+    if (R == 1) == (S == 1):
+        return False
+    T, vertical = max(R, S), S == 1
+    pad = (T - 1) // 2
+    N, _, H, W = x.shape
+    return (T in (3, 5, 7) and (ph, pw) == ((pad, 0) if vertical else (0, pad))
+            and x.shape[1] == C and C % 8 == 0 and Ko % 8 == 0
+            and tuple(dy.shape) == (N, Ko, H, W)
+            and 0 < N * H * W < 2 ** 31 and Ko * T * C < 2 ** 31
+            and (not vertical or (T - 1) * W <= 256)
+            and dy.dtype == x.dtype
+            and x.is_contiguous(memory_format=torch.channels_last)
+            and dy.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0)
+
+
+def _lineconv_wgrad_routed(x, dy, w, stride, ph, pw) -> bool:
+    """In the envelope and in a shape class where the line wgrad measured
+    faster than conv_wgrad_hw (tools/bench_lineconv.py, profiles/
+    inception_mi355x.md) by more than the row's spread: every 1xT (1.03-1.06x
+    at 17x17 1x7, 1.43-1.45x at 8x8 1x3), and Tx1 while the window fits 96
+    rows ((T-1)*W <= 32: 1.41-1.44x at 8x8 3x1). The 17x17 7x1 layers lost
+    3-4 % and longer halos were not measured. Consulted independently of
+    _lineconv_routed, by both autograd functions."""
+    if not _lineconv_wgrad_in_envelope(x, dy, w, stride, ph, pw):
         return False
     return w.shape[3] != 1 or (w.shape[2] - 1) * x.shape[3] <= 32
 

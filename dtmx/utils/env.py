@@ -24,7 +24,8 @@ Engine / debugging:
                         3x3), bn, pool, avgpool (windowed average pool), gap,
                         relu, lrn, linear, softmax, take, deconv, augment
                         (io.augment.augment_batch); lineconv sends 1xT / Tx1
-                        convs to the generic per-axis HIP path instead;
+                        convs to the generic per-axis HIP path instead (all
+                        three passes; linewgrad: their wgrad only);
                         stemconv sends the 1-4 channel first layer to the
                         zero-padded 8-channel HIP path instead
   DTMX_CHECK            1 = extra numerics checks in the op wrappers

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Line-conv microbenchmark: the factorised Inception-v3 layers (17x17 1x7 /
 7x1 at C = Ko in {128, 160, 192}; 8x8 1x3 / 3x1 at 384 -> 384 and 448 -> 384),
-fwd and dgrad, line kernels (lineconv.hip) against the generic per-axis gather
-path (conv_fwd_hw / conv_dgrad_hw) on the same inputs, timed alternately in
-one process.
+fwd, dgrad and wgrad, line kernels (lineconv.hip, lineconv_wgrad.hip) against
+the generic per-axis path (conv_fwd_hw / conv_dgrad_hw / conv_wgrad_hw) on the
+same inputs, timed alternately in one process. wgrad rows also carry the slice
+count of the line kernel's plan.
 
 Prints ms for both paths (median, [min .. max] over the rounds), the spread of
 the repeated identical rounds (max / min - 1, the larger of the two paths),
@@ -50,11 +51,14 @@ def passes(ext, x, dy, w, T, vertical):
     """{pass: (line, generic)} closures"""
     H = x.shape[2]
     ph, pw = (T // 2, 0) if vertical else (0, T // 2)
+    rs = (T, 1) if vertical else (1, T)
     return {
         "fwd": (lambda: ext.lineconv_fwd(x, w),
                 lambda: ext.conv_fwd_hw(x, w, 1, ph, pw)),
         "dgrad": (lambda: ext.lineconv_dgrad(dy, w),
                   lambda: ext.conv_dgrad_hw(dy, w, 1, ph, pw, H, H)),
+        "wgrad": (lambda: ext.lineconv_wgrad(x, dy, T, vertical),
+                  lambda: ext.conv_wgrad_hw(x, dy, *rs, 1, ph, pw)),
     }
 
 
@@ -97,18 +101,19 @@ def main():
 
     if not bitcheck(ext):
         sys.exit("bench_lineconv: bitcheck failed, no timings")
-    print(f"bitcheck ok ({len(SHAPES)} shapes x 2 orientations x fwd/dgrad, "
+    print(f"bitcheck ok ({len(SHAPES)} shapes x 2 orientations x fwd/dgrad/wgrad, "
           "line == generic)")
     print(f"batch {args.batch}, bf16 NHWC, stride 1; median of {args.rounds} "
           f"alternating rounds x {args.iters} calls [min .. max]")
     print("| HxW | C | Ko | kernel | pass | line ms | generic ms | generic/line "
-          "| spread | line TF/s | generic TF/s |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|")
+          "| spread | line TF/s | generic TF/s | slices |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
     for H, C, Ko, T in SHAPES:
         for vertical in (False, True):
             x, dy, w = make(args.batch, H, C, Ko, T, vertical)
             flop = 2.0 * args.batch * H * H * T * C * Ko
             kern = f"{T}x1" if vertical else f"1x{T}"
+            slices = ext.lineconv_wgrad_plan(Ko, C, T, vertical, args.batch, H, H)[1]
             for name, (line, generic) in passes(ext, x, dy, w, T, vertical).items():
                 for _ in range(5):  # warm both paths on this shape
                     line()
@@ -124,7 +129,8 @@ def main():
                       f"{ml:.4f} [{min(tl):.4f} .. {max(tl):.4f}] | "
                       f"{mg:.4f} [{min(tg):.4f} .. {max(tg):.4f}] | {mg / ml:.2f}x | "
                       f"{100 * spread:.1f}% | {flop / ml * 1e-9:.1f} | "
-                      f"{flop / mg * 1e-9:.1f} |", flush=True)
+                      f"{flop / mg * 1e-9:.1f} | {slices if name == 'wgrad' else ''} |",
+                      flush=True)
 
 
 if __name__ == "__main__":
