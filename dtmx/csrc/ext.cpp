@@ -51,6 +51,9 @@ at::Tensor gconv_wgrad(const at::Tensor&, const at::Tensor&, long, long, long, b
 // lineconv.hip
 at::Tensor lineconv_fwd(const at::Tensor&, const at::Tensor&);
 at::Tensor lineconv_dgrad(const at::Tensor&, const at::Tensor&);
+// colconv.hip
+at::Tensor colconv_fwd(const at::Tensor&, const at::Tensor&);
+at::Tensor colconv_dgrad(const at::Tensor&, const at::Tensor&);
 // lineconv_wgrad.hip
 at::Tensor lineconv_wgrad(const at::Tensor&, const at::Tensor&, long, bool, long);
 std::tuple<long, long> lineconv_wgrad_plan(long, long, long, bool, long, long, long);
@@ -202,6 +205,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // the (Ko,C,1,T) or (Ko,C,T,1) channels_last parameter
   m.def("lineconv_fwd", &dtmx::lineconv_fwd, py::arg("x"), py::arg("w"));
   m.def("lineconv_dgrad", &dtmx::lineconv_dgrad, py::arg("dy"), py::arg("w"));
+  // Tx1 only, any H and W (column strips: the halo lies on H alone); same
+  // operands and conventions as the line entries
+  m.def("colconv_fwd", &dtmx::colconv_fwd, py::arg("x"), py::arg("w"));
+  m.def("colconv_dgrad", &dtmx::colconv_dgrad, py::arg("dy"), py::arg("w"));
   // dw of the same conv, (Ko,C,1,T) or (Ko,C,T,1) channels_last like
   // conv_wgrad_hw: fp32 partials per pixel slice, summed in a fixed order.
   // slices = 0: the plan's count; > 0 forces it (<= ceil(N*H*W / 64)).

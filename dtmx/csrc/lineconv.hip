@@ -38,6 +38,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "dtmx_common.h"
+#include "lineconv.h"
 
 namespace dtmx {
 
@@ -322,6 +323,16 @@ static void lc_launch(const LcShape& s, const void* a, const void* b, void* out,
 #undef DTMX_LC_RUN
 }
 
+void lineconv_pack(const at::Tensor& w, at::Tensor& wp, long C, long Ko, long T) {
+  const uint32_t total = (uint32_t)(C * T * (Ko / 8));
+  DTMX_DISPATCH_16(w.scalar_type(), "lineconv_pack", {
+    lineconv_pack_kernel<elem_t>
+        <<<(total + LC_THREADS - 1) / LC_THREADS, LC_THREADS, 0, lc_stream()>>>(
+            (const elem_t*)w.data_ptr(), (elem_t*)wp.data_ptr(), total,
+            (uint32_t)C, (uint32_t)Ko, (uint32_t)T);
+  });
+}
+
 at::Tensor lineconv_fwd(const at::Tensor& x, const at::Tensor& w) {
   const LcShape s = lc_check("lineconv_fwd", "x", x, w, false);
   auto y = at::empty({s.N, s.Ko, s.H, s.W}, x.options(),
@@ -339,12 +350,8 @@ at::Tensor lineconv_dgrad(const at::Tensor& dy, const at::Tensor& w) {
                       at::MemoryFormat::ChannelsLast);
   auto wp = at::empty({s.C, s.T, s.Ko}, dy.options());
   const void* zero = lc_zero_page(dy);
-  const uint32_t total = (uint32_t)(s.C * s.T * (s.Ko / 8));
+  lineconv_pack(w, wp, s.C, s.Ko, s.T);
   DTMX_DISPATCH_16(dy.scalar_type(), "lineconv_dgrad", {
-    lineconv_pack_kernel<elem_t>
-        <<<(total + LC_THREADS - 1) / LC_THREADS, LC_THREADS, 0, lc_stream()>>>(
-            (const elem_t*)w.data_ptr(), (elem_t*)wp.data_ptr(), total,
-            (uint32_t)s.C, (uint32_t)s.Ko, (uint32_t)s.T);
     lc_launch<elem_t>(s, dy.data_ptr(), wp.data_ptr(), dx.data_ptr(), zero, s.Ko,
                       s.C);
   });

@@ -171,6 +171,59 @@ def _lineconv_routed(x, w, stride, ph, pw) -> bool:
     return w.shape[3] != 1 or (w.shape[2] - 1) * x.shape[3] <= 32
 
 
+class _ColConvNHWC(torch.autograd.Function):
+    """Tx1 same-padded stride-1 conv on the colconv.hip strip kernels (fwd,
+    dgrad); wgrad as _LineConvNHWC."""
+
+    @staticmethod
+    def forward(ctx, x, w, ph, pw):
+        ctx.save_for_backward(x, w)
+        ctx.pad = (ph, pw)
+        return require_ext().colconv_fwd(x, w)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = require_ext()
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.colconv_dgrad(dy, w)
+        if ctx.needs_input_grad[1]:
+            dw = _conv_hw_wgrad(ext, x, dy, w, 1, *ctx.pad)
+        return dx, dw, None, None
+
+
+def _colconv_in_envelope(x, w, stride, ph, pw) -> bool:
+    """The cases colconv.hip implements: Tx1 with T in {3, 5, 7}, stride 1,
+    padding ((T-1)/2, 0), C % 8 == 0, Ko % 8 == 0, a 16-byte aligned x and
+    N*H*W < 2^31. Any H and W: the strips have no halo on W."""
+    if x.dim() != 4 or w.dim() != 4 or stride != 1:
+        return False
+    Ko, C, T, S = w.shape
+    return (S == 1 and T in (3, 5, 7) and (ph, pw) == ((T - 1) // 2, 0)
+            and x.shape[1] == C and C % 8 == 0 and Ko % 8 == 0
+            and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31
+            and w.numel() < 2 ** 31
+            and w.dtype == x.dtype
+            and w.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0)
+
+
+def _colconv_routed(x, w, stride, ph, pw) -> bool:
+    """In the envelope and in a shape class where the column kernel measured
+    faster than what the call ran before it, in fwd and in dgrad, by more than
+    the row's spread (tools/bench_lineconv.py, profiles/inception_mi355x.md):
+    7x1 at 128-192 channels against the generic gather path (17x17: fwd
+    1.24-1.41x, dgrad 1.45-1.64x; 35x35, two bands: 1.42x / 1.64x; 8x44:
+    1.11x / 1.29x) and 3x1 at 8x8, 384-448 channels, against the line kernel
+    (fwd 1.22-1.24x, dgrad 1.18x). 5x1 and channel counts under the 128-wide
+    tile were not measured and are not routed."""
+    if not _colconv_in_envelope(x, w, stride, ph, pw):
+        return False
+    return w.shape[2] in (3, 7) and min(w.shape[:2]) >= 128
+
+
 def _lineconv_wgrad_in_envelope(x, dy, w, stride, ph, pw) -> bool:
     """The cases lineconv_wgrad.hip implements: the forward's envelope (the
     weight only lends its shape), a dy of x's batch and spatial size with Ko
@@ -323,8 +376,10 @@ def conv2d(x, w, stride: int = 1, padding=0, want_stats: bool = False):
     DTMX_FALLBACK=stemconv restores the zero-padded path below for both. A square call with int padding takes the dense / gather kernels with
     their fused epilogues. 1xT / Tx1 same-padded stride-1 calls take the line
     kernels where those measured faster (_lineconv_routed; DTMX_FALLBACK=
-    lineconv: the generic per-axis path); every other rectangular or per-axis
-    call takes the generic per-axis path.
+    lineconv: the generic per-axis path), except the Tx1 calls for which the
+    column strip kernels measured faster still (_colconv_routed;
+    DTMX_FALLBACK=colconv: what the call took without them); every other
+    rectangular or per-axis call takes the generic per-axis path.
 
     want_stats: also return the fused per-block BN statistic slabs
     (psum, psumsq) computed in the conv epilogue — the following BatchNorm
@@ -347,7 +402,11 @@ def conv2d(x, w, stride: int = 1, padding=0, want_stats: bool = False):
             w = F.pad(w, (0, 0, 0, 0, 0, padc))
         x = x.contiguous(memory_format=torch.channels_last)
         w = w.contiguous(memory_format=torch.channels_last)
-        if "lineconv" not in _FALLBACK and _lineconv_routed(x, w, stride, ph, pw):
+        # the column kernel first: its routing holds only classes in which it
+        # beat whatever ran before it, the line kernel at 8x8 3x1 included
+        if "colconv" not in _FALLBACK and _colconv_routed(x, w, stride, ph, pw):
+            y = _ColConvNHWC.apply(x, w, ph, pw)
+        elif "lineconv" not in _FALLBACK and _lineconv_routed(x, w, stride, ph, pw):
             y = _LineConvNHWC.apply(x, w, ph, pw)
         else:
             y = _ConvHWNHWC.apply(x, w, stride, ph, pw)

@@ -25,7 +25,10 @@ Engine / debugging:
                         relu, lrn, linear, softmax, take, deconv, augment
                         (io.augment.augment_batch); lineconv sends 1xT / Tx1
                         convs to the generic per-axis HIP path instead (all
-                        three passes; linewgrad: their wgrad only);
+                        three passes; linewgrad: their wgrad only); colconv
+                        takes the column strip kernels away from the Tx1
+                        convs routed to them (fwd and dgrad go back to the
+                        line kernels or the generic per-axis path);
                         stemconv sends the 1-4 channel first layer to the
                         zero-padded 8-channel HIP path instead
   DTMX_CHECK            1 = extra numerics checks in the op wrappers

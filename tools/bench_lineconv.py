@@ -4,12 +4,15 @@
 fwd, dgrad and wgrad, line kernels (lineconv.hip, lineconv_wgrad.hip) against
 the generic per-axis path (conv_fwd_hw / conv_dgrad_hw / conv_wgrad_hw) on the
 same inputs, timed alternately in one process. wgrad rows also carry the slice
-count of the line kernel's plan.
+count of the line kernel's plan. Tx1 rows time the column strip kernel
+(colconv.hip, fwd and dgrad) as a third path, and two Tx1-only shapes add a
+tall image (35x35, two bands) and one outside the line kernels' envelope
+(8x44, halo 264), where the line columns stay empty.
 
-Prints ms for both paths (median, [min .. max] over the rounds), the spread of
-the repeated identical rounds (max / min - 1, the larger of the two paths),
+Prints ms for the paths (median, [min .. max] over the rounds), the spread of
+the repeated identical rounds (max / min - 1, the largest of the paths),
 and achieved TF/s counted from the shape: 2 N H W T C Ko per pass, border
-taps included. A bit-for-bit check of the two paths on integer inputs runs
+taps included. A bit-for-bit check of the paths on integer inputs runs
 first; timings are refused if it fails.
 
     python tools/bench_lineconv.py [--batch 128] [--rounds 7] [--iters 200]
@@ -25,16 +28,18 @@ import torch
 
 DEV = "cuda:0"
 
-# (H = W, C, Ko, T)
-SHAPES = [(17, 128, 128, 7), (17, 160, 160, 7), (17, 192, 192, 7),
-          (8, 384, 384, 3), (8, 448, 384, 3)]
+# (H, W, C, Ko, T, orientations: vertical False = 1xT, True = Tx1)
+SHAPES = [(17, 17, 128, 128, 7, (False, True)), (17, 17, 160, 160, 7, (False, True)),
+          (17, 17, 192, 192, 7, (False, True)), (8, 8, 384, 384, 3, (False, True)),
+          (8, 8, 448, 384, 3, (False, True)), (35, 35, 192, 192, 7, (True,)),
+          (8, 44, 128, 128, 7, (True,))]
 
 
 def nhwc(t):
     return t.to(DEV).contiguous(memory_format=torch.channels_last)
 
 
-def make(N, H, C, Ko, T, vertical, ints=False, seed=0):
+def make(N, H, W, C, Ko, T, vertical, ints=False, seed=0):
     g = torch.Generator().manual_seed(seed)
     rs = (T, 1) if vertical else (1, T)
 
@@ -43,38 +48,44 @@ def make(N, H, C, Ko, T, vertical, ints=False, seed=0):
             return torch.randint(-3, 4, shape, generator=g).bfloat16()
         return (torch.randn(shape, generator=g) * scale).bfloat16()
 
-    return (nhwc(draw((N, C, H, H))), nhwc(draw((N, Ko, H, H))),
+    return (nhwc(draw((N, C, H, W))), nhwc(draw((N, Ko, H, W))),
             nhwc(draw((Ko, C) + rs, 0.05)))
 
 
 def passes(ext, x, dy, w, T, vertical):
-    """{pass: (line, generic)} closures"""
-    H = x.shape[2]
+    """{pass: {path: closure}}; a path that does not serve the shape is absent"""
+    H, W = x.shape[2:]
     ph, pw = (T // 2, 0) if vertical else (0, T // 2)
     rs = (T, 1) if vertical else (1, T)
-    return {
-        "fwd": (lambda: ext.lineconv_fwd(x, w),
-                lambda: ext.conv_fwd_hw(x, w, 1, ph, pw)),
-        "dgrad": (lambda: ext.lineconv_dgrad(dy, w),
-                  lambda: ext.conv_dgrad_hw(dy, w, 1, ph, pw, H, H)),
-        "wgrad": (lambda: ext.lineconv_wgrad(x, dy, T, vertical),
-                  lambda: ext.conv_wgrad_hw(x, dy, *rs, 1, ph, pw)),
-    }
+    out = {"fwd": {"generic": lambda: ext.conv_fwd_hw(x, w, 1, ph, pw)},
+           "dgrad": {"generic": lambda: ext.conv_dgrad_hw(dy, w, 1, ph, pw, H, W)},
+           "wgrad": {"generic": lambda: ext.conv_wgrad_hw(x, dy, *rs, 1, ph, pw)}}
+    if not vertical or (T - 1) * W <= 256:  # the line kernels' envelope
+        out["fwd"]["line"] = lambda: ext.lineconv_fwd(x, w)
+        out["dgrad"]["line"] = lambda: ext.lineconv_dgrad(dy, w)
+        out["wgrad"]["line"] = lambda: ext.lineconv_wgrad(x, dy, T, vertical)
+    if vertical:
+        out["fwd"]["col"] = lambda: ext.colconv_fwd(x, w)
+        out["dgrad"]["col"] = lambda: ext.colconv_dgrad(dy, w)
+    return out
 
 
 def bitcheck(ext):
-    """Integer inputs: both paths round the same exact fp32 sums once."""
-    ok = True
-    for H, C, Ko, T in SHAPES:
-        for vertical in (False, True):
-            x, dy, w = make(2, H, C, Ko, T, vertical, ints=True, seed=1)
-            for name, (line, generic) in passes(ext, x, dy, w, T, vertical).items():
-                good = torch.equal(line(), generic())
-                ok &= good
-                if not good:
-                    print(f"bitcheck FAILED: {name} H={H} C={C} Ko={Ko} T={T} "
-                          f"vertical={vertical}")
-    return ok
+    """Integer inputs: every path rounds the same exact fp32 sums once."""
+    ok, n = True, 0
+    for H, W, C, Ko, T, orients in SHAPES:
+        for vertical in orients:
+            x, dy, w = make(2, H, W, C, Ko, T, vertical, ints=True, seed=1)
+            for name, paths in passes(ext, x, dy, w, T, vertical).items():
+                want = paths.pop("generic")()
+                for path, fn in paths.items():
+                    good = torch.equal(fn(), want)
+                    ok &= good
+                    n += 1
+                    if not good:
+                        print(f"bitcheck FAILED: {path} {name} {H}x{W} C={C} "
+                              f"Ko={Ko} T={T} vertical={vertical}")
+    return ok, n
 
 
 def time_ms(fn, iters):
@@ -99,38 +110,50 @@ def main():
     from dtmx.ops.hip import require_ext
     ext = require_ext()
 
-    if not bitcheck(ext):
+    ok, n = bitcheck(ext)
+    if not ok:
         sys.exit("bench_lineconv: bitcheck failed, no timings")
-    print(f"bitcheck ok ({len(SHAPES)} shapes x 2 orientations x fwd/dgrad/wgrad, "
-          "line == generic)")
+    print(f"bitcheck ok ({n} line / column results == generic)")
     print(f"batch {args.batch}, bf16 NHWC, stride 1; median of {args.rounds} "
           f"alternating rounds x {args.iters} calls [min .. max]")
     print("| HxW | C | Ko | kernel | pass | line ms | generic ms | generic/line "
-          "| spread | line TF/s | generic TF/s | slices |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
-    for H, C, Ko, T in SHAPES:
-        for vertical in (False, True):
-            x, dy, w = make(args.batch, H, C, Ko, T, vertical)
-            flop = 2.0 * args.batch * H * H * T * C * Ko
+          "| spread | line TF/s | generic TF/s | slices | col ms | generic/col "
+          "| line/col | col TF/s |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for H, W, C, Ko, T, orients in SHAPES:
+        for vertical in orients:
+            x, dy, w = make(args.batch, H, W, C, Ko, T, vertical)
+            flop = 2.0 * args.batch * H * W * T * C * Ko
             kern = f"{T}x1" if vertical else f"1x{T}"
-            slices = ext.lineconv_wgrad_plan(Ko, C, T, vertical, args.batch, H, H)[1]
-            for name, (line, generic) in passes(ext, x, dy, w, T, vertical).items():
-                for _ in range(5):  # warm both paths on this shape
-                    line()
-                    generic()
+            for name, paths in passes(ext, x, dy, w, T, vertical).items():
+                for _ in range(5):  # warm every path on this shape
+                    for fn in paths.values():
+                        fn()
                 torch.cuda.synchronize()
-                tl, tg = [], []
+                ts = {p: [] for p in paths}
                 for _ in range(args.rounds):
-                    tl.append(time_ms(line, args.iters))
-                    tg.append(time_ms(generic, args.iters))
-                ml, mg = statistics.median(tl), statistics.median(tg)
-                spread = max(max(tl) / min(tl), max(tg) / min(tg)) - 1
-                print(f"| {H}x{H} | {C} | {Ko} | {kern} | {name} | "
-                      f"{ml:.4f} [{min(tl):.4f} .. {max(tl):.4f}] | "
-                      f"{mg:.4f} [{min(tg):.4f} .. {max(tg):.4f}] | {mg / ml:.2f}x | "
-                      f"{100 * spread:.1f}% | {flop / ml * 1e-9:.1f} | "
-                      f"{flop / mg * 1e-9:.1f} | {slices if name == 'wgrad' else ''} |",
-                      flush=True)
+                    for p, fn in paths.items():
+                        ts[p].append(time_ms(fn, args.iters))
+                med = {p: statistics.median(v) for p, v in ts.items()}
+                spread = max(max(v) / min(v) for v in ts.values()) - 1
+
+                def ms(p):
+                    return (f"{med[p]:.4f} [{min(ts[p]):.4f} .. {max(ts[p]):.4f}]"
+                            if p in med else "")
+
+                def ratio(p, q):
+                    return f"{med[p] / med[q]:.2f}x" if p in med and q in med else ""
+
+                def tf(p):
+                    return f"{flop / med[p] * 1e-9:.1f}" if p in med else ""
+
+                slices = (ext.lineconv_wgrad_plan(Ko, C, T, vertical, args.batch, H, W)[1]
+                          if name == "wgrad" and "line" in med else "")
+                print(f"| {H}x{W} | {C} | {Ko} | {kern} | {name} | {ms('line')} | "
+                      f"{ms('generic')} | {ratio('generic', 'line')} | "
+                      f"{100 * spread:.1f}% | {tf('line')} | {tf('generic')} | "
+                      f"{slices} | {ms('col')} | {ratio('generic', 'col')} | "
+                      f"{ratio('line', 'col')} | {tf('col')} |", flush=True)
 
 
 if __name__ == "__main__":
